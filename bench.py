@@ -4,8 +4,15 @@
 BASELINE.json metric: "passages encoded/sec + queries/sec@top-1000, 10M x 768
 corpus, 1/2/4/8 GPU".  `value` is the search half (queries/sec@top-1000, the
 north-star path: brute-force Q.D^T + top-k, BaseFaissIPRetriever.search,
-DRT/evaluator/index.py:31-33); the encode half is reported beside it under
-"encode" (passages/sec of the bf16 BERT-base passage
+DRT/evaluator/index.py:31-33).  A plain run does only that: it builds the
+corpus and the index, warms up, times --steps query batches, writes the last
+batch's results if --dump-outputs DIR is given, and prints the record.
+
+With --full the run goes on to everything else the benchmark measures or
+checks: the CPU baseline and the full-size parity checks of the search leg,
+the per-batch configuration at N > 1, and the model legs.  The encode half
+is then reported beside the search figure under "encode" (passages/sec of the
+bf16 BERT-base passage
 tower, DRModel.encode, DRT/model/biencoder.py:127-151), timed on every rank
 after the search leg (weak scaling: each rank encodes its own batches).
 
@@ -19,7 +26,7 @@ per-shard top-k (u64 score-key|id) and a device merge that certifies
 exactness; an uncertified batch is redone with the per-shard exact path
 inside the timed region.  The corpus is fixed as N grows ("scaling": "strong").
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 either
 under torch.distributed.run (WORLD_SIZE must then equal N) or directly: with
 WORLD_SIZE unset, `python bench.py --gpus N` starts the N ranks itself (one
 process per GPU, RCCL over xGMI) through a torch.distributed.run child launched
@@ -51,10 +58,19 @@ def parse():
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--qb", type=int, default=128)
     ap.add_argument("--k", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline search leg also run everything else the benchmark measures or "
+                         "checks: the CPU baselines and full-size parity checks, the per-batch configuration "
+                         "at N > 1, and the encode / rerank / query-encode / training / evaluate legs.  Off by "
+                         "default: a plain run sets up, warms up, times --steps batches and prints the record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/scores.npy (float32 [qb, k]) and DIR/ids.npy (float64 [qb, k])")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and parity checks")
     ap.add_argument("--no-encode", action="store_true",
-                    help="skip the encode leg (passages/sec of the bf16 BERT-base passage tower, every rank)")
-    ap.add_argument("--no-evaluate", action="store_true", help="skip the C2 Trainer.evaluate leg")
+                    help="with --full: skip the encode leg (passages/sec of the bf16 BERT-base passage tower, every "
+                         "rank) and the legs after it")
+    ap.add_argument("--no-evaluate", action="store_true", help="with --full: skip the C2 Trainer.evaluate leg")
     ap.add_argument("--c2-passages", type=int, default=1_000_000, help="corpus size of the C2 evaluate leg")
     ap.add_argument("--group-queries", type=int, default=-1,
                     help="queries per group of batches in search_batches (0 = per-batch path; default: "
@@ -496,6 +512,21 @@ def search_record(args, world, grouped, group_queries, kc, elapsed_s, launch_ms_
     }
 
 
+def dump_outputs(out_dir, result):
+    """--dump-outputs: the (scores, ids) that search_batches returned for the last timed batch, as
+    out_dir/scores.npy (float32 [qb, k]) and out_dir/ids.npy (float64 [qb, k]; corpus row numbers are
+    exact in float64).  Corpus and queries are seeded, so two builds run with the same arguments
+    searched the same data and their files compare element for element."""
+    import numpy as np
+    scores, ids = result
+    # at most 64 MB in all (12 bytes per entry): the first rows of a larger batch
+    rows = max(1, (64 << 20) // (12 * max(1, scores.shape[1])))
+    scores, ids = scores[:rows], ids[:rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), scores.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "ids.npy"), ids.detach().cpu().numpy().astype(np.float64))
+
+
 def encode_leg(args, device):
     import bench_legs
     return bench_legs.run(device)
@@ -600,8 +631,10 @@ def main():
     results, el, scan_ms_total, launches, (n_resolved, n_fallback, n_unc) = timed(args.warmup, nsteps)
     each_ms = timed.each_ms
     grouped = index._use_groups()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results[-1])
     sub = None
-    if world > 1 and grouped:
+    if args.full and world > 1 and grouped:
         # SURVEY §8(d)'s HBM-bound configuration beside the product default: the same protocol with one
         # 128-query batch per group (one filter launch per batch)
         gq_saved = srch.GROUP_QUERIES
@@ -632,16 +665,18 @@ def main():
         out["order_uncertified_queries"] = int(n_unc)
         out["uncertified_queries_resolved"] = int(n_resolved)
         out["global_tau_fallback_batches"] = int(n_fallback)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, shard, queries[args.warmup], results[0])
-        elif world > 1 and not args.no_cpu_baseline:
+        elif args.full and world > 1 and not args.no_cpu_baseline:
             out["parity_union_fp64"] = union_parity(args, queries[args.warmup], results[0], dev)
     # the search leg's 15 GB corpus, index and results leave HBM before the model legs (the training
     # legs' torch baselines reserve ~140 GB)
     del shard, queries, results, index, local_index
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
-    enc = None if args.no_encode else encode_leg(args, dev)
+    # a plain run ends with the headline record; every other leg runs under --full
+    model_legs = args.full and not args.no_encode
+    enc = encode_leg(args, dev) if model_legs else None
     if enc is not None:
         if world > 1:
             # aggregate over ranks: every rank encodes its own batches; slowest rank sets the rate
@@ -655,7 +690,7 @@ def main():
             rf["frac"] = round(rf["achieved"] / rf["peak"], 4)
         if out is not None:
             out["encode"] = enc
-    if rank == 0 and not args.no_encode and world == 1:
+    if rank == 0 and model_legs and world == 1:
         import bench_legs as bench_encode
         if not args.no_cpu_baseline:
             out["encode"]["cpu_baseline"] = encode_cpu_baseline()

@@ -120,6 +120,31 @@ def test_bench_corpus_union_of_shards_is_the_world1_corpus(world, monkeypatch):
     assert torch.equal(torch.cat([p[0] for p in parts]).view(torch.int16), full.view(torch.int16))
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_last_step_as_float_arrays(tmp_path):
+    """--dump-outputs: scores as float32, ids as float64 (row numbers stay exact), same shapes as returned."""
+    import numpy as np
+    import torch
+    import bench
+    scores = torch.arange(12, dtype=torch.float32).reshape(3, 4) / 7
+    ids = torch.tensor([[9_999_999, 1 << 40, -1, 0]] * 3, dtype=torch.int64)
+    out = tmp_path / "dump" / "nested"
+    bench.dump_outputs(str(out), (scores, ids))
+    s, i = np.load(out / "scores.npy"), np.load(out / "ids.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64
+    assert np.array_equal(s, scores.numpy()) and np.array_equal(i.astype(np.int64), ids.numpy())
+    assert sorted(p.name for p in out.iterdir()) == ["ids.npy", "scores.npy"]
+
+
 def test_per_shape_roofline_of_a_20_step_run():
     """The driver's --steps 20 runs a 2048-query group and a 512-query group: the record reports each
     launch shape's own average and fraction beside the mixed average."""

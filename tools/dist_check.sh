@@ -11,7 +11,7 @@ fi
 timeout -k 10 600 python tools/sim_dist.py --world ${WORLD:-8} --steps 20 --check > $OUT/sim_dist.log 2>&1 || { echo "sim rc=$?"; tail -20 $OUT/sim_dist.log; exit 3; }
 tail -1 $OUT/sim_dist.log
 DRT_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --n-corpus 2000000 \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 5 --warmup 2 --n-corpus 2000000 \
   > $OUT/gloo2.log 2>&1 || { echo "gloo rc=$?"; tail -20 $OUT/gloo2.log; exit 4; }
 grep '^{' $OUT/gloo2.log | cut -c1-300
 for st in 1 2 3; do

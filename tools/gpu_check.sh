@@ -5,6 +5,7 @@
 # measurement steps run.
 set -u
 cd "$(dirname "$0")/.."
+R=$(pwd)
 OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
@@ -27,13 +28,13 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "STOP: pytest rc=$rc"; exit $rc; fi
 fi
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-run bench 600 python bench.py --steps $STEPS --warmup 3 ${BENCH_ARGS:-} || exit $?
+run bench 600 python bench.py --full --steps $STEPS --warmup 3 ${BENCH_ARGS:-} || exit $?
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench_$TAG.json
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   cd /tmp
   run_prof() {
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/prof_$TAG -o run --output-format csv \
-      -- python3 $GRAFT_REPO_ROOT/bench.py --steps $STEPS --warmup 3 --no-cpu-baseline > $GRAFT_REPO_ROOT/$OUT/prof_$TAG.log 2>&1
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof_$TAG -o run --output-format csv \
+      -- python3 $R/bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline > $R/$OUT/prof_$TAG.log 2>&1
   }
   run_prof; rc=$?
   echo "=== rocprof rc=$rc" | tee -a $GRAFT_REPO_ROOT/$OUT/session.log

@@ -6,7 +6,7 @@
 # Steps:
 #   tests        pytest -m gpu over ${TEST_PATHS:-tests}
 #   smoke        __graft_entry__.smoke()
-#   bench        the driver's bench line (N = 1), ${BENCH_ARGS}
+#   bench        the full bench line (N = 1, bench.py --full: every leg), ${BENCH_ARGS}
 #   bench_search bench.py search leg only (no encode / evaluate / CPU baseline)
 #   bench_gloo2  `bench.py --gpus 2` with no launcher: two ranks on the one GPU over gloo
 #   prof_bench   rocprofv3 --kernel-trace --stats of the search-only bench
@@ -51,12 +51,12 @@ for s in "$@"; do
     tests) step tests ${TEST_TIMEOUT:-900} python3 -u -m pytest ${TEST_PATHS:-tests} -m gpu -v -rfE \
              --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} || exit $? ;;
     smoke) step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) step bench ${BENCH_TIMEOUT:-900} python3 -u bench.py --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} || exit $?
+    bench) step bench ${BENCH_TIMEOUT:-900} python3 -u bench.py --full --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} || exit $?
            grep '^{' $OUT/${TAG}_bench.log | tail -1 > $OUT/${TAG}_bench.json ;;
     bench_search) step bench_search 300 python3 -u bench.py --steps ${STEPS:-30} --warmup 3 --no-cpu-baseline \
              --no-encode ${BENCH_ARGS:-} || exit $? ;;
     bench_gloo2) DRT_BENCH_BACKEND=gloo step bench_gloo2 600 python3 -u bench.py --gpus 2 --n-corpus 2000000 \
-             --steps 8 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} || exit $? ;;
+             --full --steps 8 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} || exit $? ;;
     prof_bench) prof prof_bench 600 $R/bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-evaluate --no-encode \
                   ${BENCH_ARGS:-} || exit $? ;;
     prof_c2) LAST=${LAST:-800} prof prof_c2 600 $R/tools/search_ab.py --n 1000000 --steps 78 --rounds 2 \
