@@ -46,6 +46,10 @@ _SIGNATURES = [
                                         c_sz, c_vp]),
     ("drt_ip_topk_dist_filter_chunks", c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp,
                                                c_vp, c_i32, c_vp, c_sz, c_vp]),
+    ("drt_ip_topk_tighten_rank", c_i32, [c_i64, c_i32, c_i32]),
+    ("drt_ip_topk_filter_passes_workspace", c_sz, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    ("drt_ip_topk_filter_passes", c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp,
+                                          c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("drt_ip_topk_dist_filter_lists", c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_i32,
                                               c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("drt_ip_topk_dist_filter_lists_at", c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp,

@@ -61,7 +61,16 @@ struct ScanArgs {
   int64_t cap;
   int64_t exp_hits;   // FILTER: expected hits per query (0: cap / 4); picks the append flavour
   uint32_t row_base;  // FILTER (lean kernels): added to the row of every hit key (a chunk of a longer shard)
+  // FILTER (lean kernels): an interleaved pass over the shard -- the launch covers the 16-row tiles t with
+  // t % npass == pass (npass <= 1: every tile); nrows stays the shard's row count, hit rows are shard rows
+  int32_t npass;
+  int32_t pass;
 };
+
+// The tiles of an interleaved pass (ScanArgs::npass / pass) out of a shard's `ntiles`.
+__host__ __device__ __forceinline__ int pass_tiles(int ntiles, int npass, int pass) {
+  return npass <= 1 ? ntiles : (pass < ntiles ? (ntiles - 1 - pass) / npass + 1 : 0);
+}
 
 // LDS-DMA of 16 B per lane.  Issued through inline asm on purpose: with the
 // builtin, hipcc cannot prove the ring slots disjoint and waits vmcnt(0)
@@ -613,18 +622,23 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
   uint8_t* hq = (uint8_t*)(smem + C::HIT_Q_OFF) + wave * kWaveSeg;
 
   const int64_t qbase = (int64_t)blockIdx.y * kQueriesPerWG;
-  // tile and row indices in 32 bits (rows < 2^32: the hit keys carry 32-bit rows)
-  const int ntiles = (int)((a.nrows + kT16 - 1) / kT16);
+  // tile and row indices in 32 bits (rows < 2^32: the hit keys carry 32-bit rows).  An interleaved pass
+  // (npass > 1) runs over its own tiles j = 0 .. ntiles - 1, which are the shard's tiles j * tmul + tph
+  const int tmul = a.npass > 1 ? a.npass : 1;
+  const int tph = a.npass > 1 ? a.pass : 0;
+  const int tall = (int)((a.nrows + kT16 - 1) / kT16);
+  const int ntiles = pass_tiles(tall, a.npass, a.pass);
   const uint32_t nrows = (uint32_t)a.nrows;
   const int t0 = blockIdx.x;
   const int tstep = gridDim.x;
   const int my_tiles = t0 < ntiles ? (ntiles - 1 - t0) / tstep + 1 : 0;
   if (my_tiles == 0) return;
-  const int partial_tile = (a.nrows & (kT16 - 1)) != 0 ? ntiles - 1 : -1;
+  // (the shard's short last tile belongs to exactly one pass)
+  const int partial_tile = ((a.nrows & (kT16 - 1)) != 0 && (tall - 1) % tmul == tph) ? ntiles - 1 : -1;
   const uint32_t ring = lds_addr_of(smem);
   // the next tile to issue, as a row pointer advanced by a constant (scalar) stride per tile
-  const int64_t tile_stride = (int64_t)tstep * kT16 * a.ldp * 2;
-  const char* next_base = (const char*)(a.P + (int64_t)t0 * kT16 * a.ldp);
+  const int64_t tile_stride = (int64_t)tstep * tmul * kT16 * a.ldp * 2;
+  const char* next_base = (const char*)(a.P + ((int64_t)t0 * tmul + tph) * kT16 * a.ldp);
 
   // 16 queries per wave: qbase + 16 * wave + r
   const int64_t qw = qbase + wave * 16;
@@ -655,7 +669,8 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
   for (int p = 0; p < PD; ++p) {
     if (p < my_tiles) {
       const int tile = t0 + p * tstep;
-      lt.template issue<NT>(a, ring + p * C::TILE_BYTES, next_base, tile == partial_tile, tile, wave, lane);
+      lt.template issue<NT>(a, ring + p * C::TILE_BYTES, next_base, tile == partial_tile, tile * tmul + tph, wave,
+                            lane);
       next_base += tile_stride;
     }
   }
@@ -756,13 +771,14 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
     lds_barrier();   // tile it+1 landed (every wave's share); slot(it) fully read
     if (it + PD < my_tiles) {
       const int ntile = tile + PD * tstep;
-      lt.template issue<NT>(a, ring + buf * C::TILE_BYTES, next_base, ntile == partial_tile, ntile, wave, lane);
+      lt.template issue<NT>(a, ring + buf * C::TILE_BYTES, next_base, ntile == partial_tile, ntile * tmul + tph,
+                            wave, lane);
       next_base += tile_stride;
     }
     const int nslot = buf + 1 == C::NBUF ? 0 : buf + 1;
     mma_roll(acc, nslot);
     if (it > 0) epilogue(prev, rb_prev);
-    rb = (uint32_t)tile * kT16 + 4 * kq;
+    rb = (uint32_t)(tile * tmul + tph) * kT16 + 4 * kq;
     buf = nslot;
   };
   for (int it = 0; it < my_tiles; it += 2) {
@@ -825,16 +841,20 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   uint8_t* hq = (uint8_t*)(smem + C32::RING_BYTES + kHitCap * 8) + wave * kSeg;
 
   const int64_t qbase = (int64_t)blockIdx.y * kQueriesPerWG32;
-  const int ntiles = (int)((a.nrows + kT16 - 1) / kT16);
+  // (an interleaved pass: its tiles j = 0 .. ntiles - 1 are the shard's tiles j * tmul + tph, as in ip_scan16r)
+  const int tmul = a.npass > 1 ? a.npass : 1;
+  const int tph = a.npass > 1 ? a.pass : 0;
+  const int tall = (int)((a.nrows + kT16 - 1) / kT16);
+  const int ntiles = pass_tiles(tall, a.npass, a.pass);
   const uint32_t nrows = (uint32_t)a.nrows;
   const int t0 = blockIdx.x;
   const int tstep = gridDim.x;
   const int my_tiles = t0 < ntiles ? (ntiles - 1 - t0) / tstep + 1 : 0;
   if (my_tiles == 0) return;
-  const int partial_tile = (a.nrows & (kT16 - 1)) != 0 ? ntiles - 1 : -1;
+  const int partial_tile = ((a.nrows & (kT16 - 1)) != 0 && (tall - 1) % tmul == tph) ? ntiles - 1 : -1;
   const uint32_t ring = lds_addr_of(smem);
-  const int64_t tile_stride = (int64_t)tstep * kT16 * a.ldp * 2;
-  const char* next_base = (const char*)(a.P + (int64_t)t0 * kT16 * a.ldp);
+  const int64_t tile_stride = (int64_t)tstep * tmul * kT16 * a.ldp * 2;
+  const char* next_base = (const char*)(a.P + ((int64_t)t0 * tmul + tph) * kT16 * a.ldp);
 
   // 32 queries per wave: qw + 16 b + r, b = 0, 1
   const int64_t qw = qbase + wave * 32;
@@ -872,7 +892,8 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   for (int p = 0; p < PD; ++p) {
     if (p < my_tiles) {
       const int tile = t0 + p * tstep;
-      lt.template issue<false>(a, ring + p * C::TILE_BYTES, next_base, tile == partial_tile, tile, wave, lane);
+      lt.template issue<false>(a, ring + p * C::TILE_BYTES, next_base, tile == partial_tile, tile * tmul + tph, wave,
+                               lane);
       next_base += tile_stride;
     }
   }
@@ -958,14 +979,14 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
       af[s % RD] = s + RD < KS ? frag(buf, s + RD) : frag(nslot, s + RD - KS);
       __builtin_amdgcn_sched_barrier(0);
       if (s == KS / 4 && do_dma) {
-        lt.template issue<false>(a, ring + pslot * C::TILE_BYTES, next_base, ntile == partial_tile, ntile, wave,
-                                 lane);
+        lt.template issue<false>(a, ring + pslot * C::TILE_BYTES, next_base, ntile == partial_tile,
+                                 ntile * tmul + tph, wave, lane);
         next_base += tile_stride;
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     if (it > 0) epilogue(prev0, prev1, rb_prev);
-    rb = (uint32_t)tile * kT16 + 4 * kq;
+    rb = (uint32_t)(tile * tmul + tph) * kT16 + 4 * kq;
     buf = nslot;
   };
   f32x4 a0, a1, b0, b1;
@@ -1028,6 +1049,11 @@ struct SelectArgs {
   uint64_t* out_packed;
   bool global_tau;
   int k_cert;               // k of the certification (0: k); the refine stage selects kc >= k entries
+  // packed output of a filter whose later passes ran against a tightened threshold (tighten_kernel):
+  // [nq][4] u32 = the first pass's hit count c0, r_eff = its hits >= tau1, tightened (tau1 > tau0).  The
+  // list then holds every row >= tau1 plus first-pass rows in [tau0, tau1): it is the whole shard's list
+  // only if r_eff + (hits of the later passes) >= k -- otherwise flag bit 0 is set (not certified)
+  const uint32_t* pass0;
 };
 
 template <int INPUT>
@@ -1488,8 +1514,12 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
       const uint64_t nval = (uint64_t)(kk_total < a.k ? kk_total : a.k);
       // bit 0: overflow (more hits than the list buffer held); bit 1: truncated (more hits than the k
       // entries written -- what a merge of capped exchange lists certifies against, round 6)
-      op[a.k] = (nval << 32) | ((INPUT == SEL_KEYS64 && c_raw > a.cap) ? 1ull : 0ull) |
-                (c_raw > (int64_t)a.k ? 2ull : 0ull);
+      bool bad = INPUT == SEL_KEYS64 && c_raw > a.cap;
+      if (INPUT == SEL_KEYS64 && a.pass0) {
+        const uint32_t* t = a.pass0 + q * 4;
+        if (t[2] && (int64_t)t[1] + (c_raw - (int64_t)t[0]) < (int64_t)a.k) bad = true;
+      }
+      op[a.k] = (nval << 32) | (bad ? 1ull : 0ull) | (c_raw > (int64_t)a.k ? 2ull : 0ull);
     }
     return;
   }
@@ -1513,6 +1543,93 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
       if (!a.global_tau && c_raw < kq && c_raw < a.n_total) st = 1;                    // threshold too high
     }
     a.status[orow] = st;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Tightened threshold after the first of a shard's interleaved filter passes
+// (drt_ip_topk_filter_passes): tau1[q] = the score of the r-th best key the first pass
+// collected (exactly: MSD radix select on the 32-bit score key, 8 bits per step) when it
+// collected c0 >= r of them, else tau0[q] (also for an inactive query, tau0 = NaN, and for a
+// list that overflowed `cap`).  pass0[q] = {c0, r_eff = first-pass keys scoring >= tau1 (ties
+// count), tau1 > tau0, 0}: what the final select certifies the list with (SelectArgs::pass0).
+// One block per query; the list (~cap / 4 / passes keys) is read from L2 five times.
+// ---------------------------------------------------------------------------
+constexpr int kTightThreads = 256;
+
+__global__ __launch_bounds__(kTightThreads) void tighten_kernel(const uint64_t* keys, int64_t cap,
+                                                                const uint32_t* counts, const float* tau0, int r,
+                                                                float* tau1, uint32_t* pass0) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t sh_prefix, sh_rem;
+  __shared__ uint32_t red[kTightThreads / 64];
+  const int tid = threadIdx.x;
+  const int64_t q = blockIdx.x;
+  const uint32_t c = counts[q * kCntStride];
+  const float t0 = tau0[q];
+  if (!((int64_t)c <= cap && c >= (uint32_t)r && t0 == t0)) {
+    if (tid == 0) {
+      tau1[q] = t0;
+      pass0[q * 4 + 0] = c;
+      pass0[q * 4 + 1] = c;
+      pass0[q * 4 + 2] = 0;
+      pass0[q * 4 + 3] = 0;
+    }
+    return;
+  }
+  const uint64_t* kq = keys + q * cap;
+  uint32_t prefix = 0, mask = 0, rem = (uint32_t)r;   // the rem-th smallest key among those matching prefix
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    for (uint32_t j = tid; j < c; j += kTightThreads) {
+      const uint32_t key = (uint32_t)(kq[j] >> 32);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {
+      const uint32_t bb[4] = {hist[4 * tid], hist[4 * tid + 1], hist[4 * tid + 2], hist[4 * tid + 3]};
+      const uint32_t s4 = bb[0] + bb[1] + bb[2] + bb[3];
+      uint32_t incl = s4;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_up(incl, o, 64);
+        if (tid >= o) incl += v;
+      }
+      uint32_t run = incl - s4;
+      if (run < rem && rem <= incl) {   // exactly one lane: at least rem keys match the prefix
+        int dgt = 4 * tid;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          if (dgt == 4 * tid + t && run + bb[t] < rem) {
+            run += bb[t];
+            ++dgt;
+          }
+        }
+        sh_prefix = prefix | ((uint32_t)dgt << shift);
+        sh_rem = rem - run;
+      }
+    }
+    __syncthreads();
+    prefix = sh_prefix;
+    rem = sh_rem;
+    mask |= 255u << shift;
+  }
+  const float t1 = desc_key_to_score(prefix);
+  uint32_t n = 0;
+  for (uint32_t j = tid; j < c; j += kTightThreads) n += key_score(kq[j]) >= t1 ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = n;
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t tot = 0;
+    for (int w = 0; w < kTightThreads / 64; ++w) tot += red[w];
+    tau1[q] = t1;
+    pass0[q * 4 + 0] = c;
+    pass0[q * 4 + 1] = tot;
+    pass0[q * 4 + 2] = t1 > t0 ? 1u : 0u;
+    pass0[q * 4 + 3] = 0;
   }
 }
 
@@ -3495,8 +3612,13 @@ static dim3 scan16_grid(int64_t nq, int64_t nrows) {
 template <int D>
 static int launch_scan_d(const ScanArgs& a, int mode, hipStream_t s) {
   if (a.nq == 0 || a.nrows == 0) return DRT_OK;
-  const int64_t ntiles = (a.nrows + kT16 - 1) / kT16;
-  const dim3 grid = scan16_grid(a.nq, a.nrows);
+  // an interleaved pass (the lean filter kernels only) is gridded over its own tiles
+  if (a.npass > 1 && (mode != SCAN_FILTER || D > 768 || a.row0 != 0 || a.rstride != 1 || a.pass < 0 ||
+                      a.pass >= a.npass))
+    return DRT_EINVAL;
+  const int64_t ntiles = pass_tiles((int)((a.nrows + kT16 - 1) / kT16), a.npass, a.pass);
+  if (ntiles == 0) return DRT_OK;
+  const dim3 grid = scan16_grid(a.nq, ntiles * kT16);
   const unsigned gy = grid.y;
   if (mode == SCAN_FILTER) {
     // 8 waves (2 per SIMD), 16 queries each; fragment reads of the next tile rolled into this
@@ -4433,6 +4555,118 @@ int drt_ip_topk_dist_filter_chunks(const void* Q, int64_t nq, const void* P, int
   sa.counts = cnt;
   sa.cap = p.cap;
   sa.n_total = n_local;
+  return launch_select(sa, SEL_KEYS64, SEL_TOPK, s);
+}
+
+// Rank of the tightened threshold (drt_ip_topk_filter_passes): with C = shard tiles / first-pass tiles, the
+// rows at or above the first pass's r-th best score number C r on average over the shard, with standard
+// deviation sqrt(C (C - 1) r + (C - 1) r) (the order statistic's relative 1 / sqrt(r) on the tail
+// probability, plus the Poisson count of the other passes' rows); the smallest r that keeps the mean 5
+// sigma above k.  0: nothing to tighten (one pass, or the first pass holds every tile).
+int32_t drt_ip_topk_tighten_rank(int64_t n_local, int32_t npasses, int32_t k) {
+  if (n_local <= 0 || npasses <= 1 || k < 1) return 0;
+  const int64_t tall = (n_local + kT16 - 1) / kT16;
+  const int64_t t0 = (tall + npasses - 1) / npasses;   // tiles t % npasses == 0
+  if (t0 >= tall) return 0;
+  const double C = (double)tall / (double)t0;
+  for (int64_t r = 1; r < ((int64_t)1 << 24); ++r) {
+    const double sigma = std::sqrt(C * (C - 1.0) * (double)r + (C - 1.0) * (double)r);
+    if (C * (double)r - 5.0 * sigma >= (double)k) return (int32_t)r;
+  }
+  return 0;
+}
+
+size_t drt_ip_topk_filter_passes_workspace(int64_t nq, int64_t n_local, int64_t n_global, int32_t d, int32_t k) {
+  if (!valid_dist_dims(nq, n_local, n_global, d, k)) return 0;
+  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
+  return align_up(p.total, 256) + (size_t)p.nq_pad * 16;
+}
+
+// dist_filter over a shard as `npasses` interleaved passes with ONE hit list and ONE select: pass p is
+// one scan launch over the 16-row tiles t with t % npasses == p (a strided sample of the shard, like the
+// sample pass's rows -- not its first rows, which a corpus ordered by source or topic makes
+// unrepresentative).  Pass 0 filters against tau; tighten_kernel then raises each query's threshold to
+// tau1 = its r-th best collected score (r > 0; r < 0: drt_ip_topk_tighten_rank; 0: every pass against
+// tau) and passes 1.. filter against tau1, appending to the same lists.  A tightened list holds every row
+// >= tau1 plus pass-0 rows in [tau, tau1), so the select certifies it by r_eff + (later passes' hits) >=
+// k (SelectArgs::pass0): then its best k keys all score >= tau1 and the packed list equals
+// drt_ip_topk_dist_filter's over the whole shard; otherwise flag bit 0 is set and the merge leaves the
+// query uncertified.  tau1_out [nq] / pass0_out [nq][4] (c0, r_eff, tightened, 0): optional copies.
+// d <= 768 (the lean filter kernels).  Meant for a shard that is the whole corpus: under a global
+// threshold of several shards a short local list is normal and a local r-th best proves nothing.
+int drt_ip_topk_filter_passes(const void* Q, int64_t nq, const void* P, int64_t n_local, int64_t n_global,
+                              int32_t d, int32_t k, int64_t id_offset, const float* tau, uint64_t* packed,
+                              int32_t npasses, int32_t r, float* tau1_out, uint32_t* pass0_out, void* ws,
+                              size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(valid_dist_dims(nq, n_local, n_global, d, k));
+  DRT_REQUIRE(id_offset >= 0 && id_offset + n_local <= n_global);
+  DRT_REQUIRE(d <= 768 && n_local < ((int64_t)1 << 32) && npasses >= 1 && npasses <= 1024);
+  if (nq == 0) return DRT_OK;
+  DRT_REQUIRE(Q && tau && packed && ws);
+  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
+  const size_t off_pass0 = align_up(p.total, 256);
+  DRT_REQUIRE(ws_bytes >= off_pass0 + (size_t)p.nq_pad * 16);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = (char*)ws;
+  uint32_t* cnt = (uint32_t*)(w + p.off_cnt);
+  SelectArgs sa{};
+  sa.in = w + p.off_keys;
+  sa.in_stride = p.cap;
+  sa.k = k;
+  sa.nq = nq;
+  sa.id_offset = id_offset;
+  sa.out_packed = packed;
+  sa.global_tau = true;
+  if (r < 0) r = drt_ip_topk_tighten_rank(n_local, npasses, k);
+  const int tall = (int)((n_local + kT16 - 1) / kT16);
+  const bool tighten = r > 0 && n_local > 0 && pass_tiles(tall, npasses, 0) < tall;
+  if (!tighten) {
+    if (tau1_out) DRT_CHECK_HIP(hipMemcpyAsync(tau1_out, tau, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
+    if (pass0_out) DRT_CHECK_HIP(hipMemsetAsync(pass0_out, 0, (size_t)nq * 16, s));
+  }
+  if (n_local == 0) {
+    sa.n_in = 0;
+    sa.n_total = 0;
+    return launch_select(sa, SEL_DENSE32, SEL_TOPK, s);
+  }
+  DRT_REQUIRE(P != nullptr);
+  DRT_CHECK_HIP(hipMemsetAsync(cnt, 0, p.nq_pad * 4 * kCntStride, s));
+  float* tau1 = tau1_out ? tau1_out : (float*)(w + p.off_tau);
+  uint32_t* pass0 = pass0_out ? pass0_out : (uint32_t*)(w + off_pass0);
+  const int64_t target = std::max<int64_t>(4096, 4 * (int64_t)k);
+  for (int ps = 0; ps < npasses; ++ps) {
+    if (pass_tiles(tall, npasses, ps) == 0) continue;
+    ScanArgs a{};
+    a.Q = (const __bf16*)Q;
+    a.nq = nq;
+    a.ldq = d;
+    a.P = (const __bf16*)P;
+    a.ldp = d;
+    a.row0 = 0;
+    a.nrows = n_local;
+    a.rstride = 1;
+    a.tau = (tighten && ps > 0) ? tau1 : tau;
+    a.counts = cnt;
+    a.out = w + p.off_keys;
+    a.cap = p.cap;
+    a.exp_hits = p.sample ? std::max<int64_t>(1, target * n_local / npasses / std::max<int64_t>(1, n_global))
+                          : std::max<int64_t>(1, n_local / npasses);
+    a.npass = npasses;
+    a.pass = ps;
+    const int rc = launch_scan(a, d, SCAN_FILTER, s, PROF_SCAN);
+    if (rc) return rc;
+    if (tighten && ps == 0) {
+      const ProfPair pp = prof_begin(PROF_SELECT, s);
+      hipLaunchKernelGGL(tighten_kernel, dim3((unsigned)nq), dim3(kTightThreads), 0, s,
+                         (const uint64_t*)(w + p.off_keys), p.cap, (const uint32_t*)cnt, tau, (int)r, tau1, pass0);
+      prof_end(pp, s);
+      DRT_CHECK_HIP(hipGetLastError());
+    }
+  }
+  sa.counts = cnt;
+  sa.cap = p.cap;
+  sa.n_total = n_local;
+  sa.pass0 = tighten ? pass0 : nullptr;
   return launch_select(sa, SEL_KEYS64, SEL_TOPK, s);
 }
 

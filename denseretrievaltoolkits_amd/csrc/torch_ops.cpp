@@ -450,6 +450,46 @@ void dist_filter_chunks_into(const Tensor& q_, const Tensor& p_, int64_t n_globa
            "drt_ip_topk_dist_filter_chunks");
 }
 
+// dist_filter over a shard that is the whole corpus as `npasses` interleaved passes (pass p = the 16-row
+// tiles t with t % npasses == p), the passes after the first against each query's tightened threshold
+// (drt_ip_topk_filter_passes; r < 0: the default rank, 0: no tightening).  tau1 [nq] fp32 and pass0
+// [nq, 4] int32 (pass-0 hit count, r_eff, tightened, 0), when given, receive the tightened state.
+void filter_passes_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
+                        const Tensor& tau_, int64_t npasses, int64_t r, Tensor& packed,
+                        const c10::optional<Tensor>& tau1, const c10::optional<Tensor>& pass0) {
+  need(q_, "q", at::kBFloat16, 2);
+  need(p_, "p", at::kBFloat16, 2);
+  need(tau_, "tau", at::kFloat, 1);
+  need(packed, "packed", at::kLong, 2);
+  const c10::DeviceGuard g(q_.device());
+  const Tensor q = q_.contiguous(), p = p_.contiguous(), tau = tau_.contiguous();
+  TORCH_CHECK_VALUE(tau.size(0) == q.size(0), "tau must hold one threshold per query");
+  TORCH_CHECK_VALUE(packed.is_contiguous() && packed.size(0) == q.size(0) && packed.size(1) == k + 1,
+                    "packed must be a contiguous [nq, k + 1] tensor");
+  TORCH_CHECK_VALUE(q.size(1) <= 768, "interleaved filter passes take d <= 768");
+  TORCH_CHECK_VALUE(npasses >= 1 && npasses <= 1024, "npasses must be in [1, 1024]");
+  if (tau1.has_value()) {
+    need(*tau1, "tau1", at::kFloat, 1);
+    TORCH_CHECK_VALUE(tau1->is_contiguous() && tau1->size(0) == q.size(0), "tau1 must be a contiguous [nq] tensor");
+  }
+  if (pass0.has_value()) {
+    need(*pass0, "pass0", at::kInt, 2);
+    TORCH_CHECK_VALUE(pass0->is_contiguous() && pass0->size(0) == q.size(0) && pass0->size(1) == 4,
+                      "pass0 must be a contiguous [nq, 4] tensor");
+  }
+  const size_t wsb = drt_ip_topk_filter_passes_workspace(q.size(0), p.size(0), n_global, (int32_t)q.size(1), (int32_t)k);
+  TORCH_CHECK_VALUE(wsb > 0 || q.size(0) == 0, "unsupported dist shape nq=", q.size(0), " n_local=", p.size(0),
+                    " n_global=", n_global, " d=", q.size(1), " k=", k);
+  Tensor ws = workspace(q, wsb);
+  check_rc(drt_ip_topk_filter_passes(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0), n_global,
+                                     (int32_t)q.size(1), (int32_t)k, id_offset, tau.data_ptr<float>(),
+                                     (uint64_t*)packed.data_ptr<int64_t>(), (int32_t)npasses, (int32_t)r,
+                                     tau1.has_value() ? tau1->data_ptr<float>() : nullptr,
+                                     pass0.has_value() ? (uint32_t*)pass0->data_ptr<int32_t>() : nullptr,
+                                     ws.data_ptr(), wsb, stream_of(q)),
+           "drt_ip_topk_filter_passes");
+}
+
 // dist_filter_lists for query rows [q0, q0 + nq) of lists [nlists, NQ, r] gathered for a group of
 // batches, writing the packed lists into `packed` ([nq, k + 1], e.g. a row slice of a group buffer).
 void dist_filter_lists_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
@@ -677,6 +717,8 @@ TORCH_LIBRARY(drt, m) {
   m.def("dist_filter_into(Tensor q, Tensor p, int n_global, int k, int id_offset, Tensor tau, Tensor(a!) packed) -> ()");
   m.def("dist_filter_chunks_into(Tensor q, Tensor p, int n_global, int k, int id_offset, Tensor tau, int[] starts, "
         "Tensor(a!) packed) -> ()");
+  m.def("filter_passes_into(Tensor q, Tensor p, int n_global, int k, int id_offset, Tensor tau, int npasses, int r, "
+        "Tensor(a!) packed, Tensor(b!)? tau1=None, Tensor(c!)? pass0=None) -> ()");
   m.def("merge_packed(Tensor parts, int k, int n_global, int k_cert=-1) -> (Tensor, Tensor, Tensor)");
   m.def("score_ce_fwd(Tensor q, Tensor p, int target_stride, float scale) -> (Tensor, Tensor, Tensor)");
   m.def("score_ce_bwd(Tensor grad, Tensor q, Tensor p, Tensor scores, Tensor lse, int target_stride, "
@@ -694,6 +736,7 @@ TORCH_LIBRARY_IMPL(drt, CUDA, m) {   // the GPU dispatch key of torch-ROCm
   m.impl("ip_topk", &ip_topk);
   m.impl("ip_topk.out", &ip_topk_out);
   m.impl("dist_filter_chunks_into", &dist_filter_chunks_into);
+  m.impl("filter_passes_into", &filter_passes_into);
   m.impl("ip_topk_resolve", &ip_topk_resolve);
   m.impl("ip_topk_resolve_wide", &ip_topk_resolve_wide);
   m.impl("ip_topk_large", &ip_topk_large);

@@ -357,6 +357,27 @@ def dist_filter_chunks_into(q: torch.Tensor, p: torch.Tensor, n_global: int, k: 
     ops.load().dist_filter_chunks_into(q, p, n_global, k, id_offset, tau, [int(x) for x in starts], packed)
 
 
+def tighten_rank(n_local: int, npasses: int, k: int) -> int:
+    """Rank r of the tightened threshold of ``filter_passes_into`` (host arithmetic, include/drt.h): the
+    smallest r that keeps C r, the mean number of rows at or above the first pass's r-th best score, 5 sigma
+    above k (C = shard tiles / first-pass tiles); 0 = nothing to tighten."""
+    return int(_native.load().drt_ip_topk_tighten_rank(n_local, npasses, k))
+
+
+def filter_passes_into(q: torch.Tensor, p: torch.Tensor, n_global: int, k: int, id_offset: int, tau: torch.Tensor,
+                       npasses: int, packed: torch.Tensor, r: int = -1, tau1: Optional[torch.Tensor] = None,
+                       pass0: Optional[torch.Tensor] = None) -> None:
+    """dist_filter_into over ``p`` (a shard that is the whole corpus, d <= 768) as ``npasses`` interleaved
+    passes -- pass j scans the 16-row tiles t with t % npasses == j -- with one hit list and one select.
+    Pass 0 filters against ``tau``, the later ones against each query's r-th best pass-0 score (``r`` < 0:
+    ``tighten_rank``; 0: no tightening).  The packed lists equal dist_filter_into's over all of ``p``,
+    except that a tightened query with fewer than k rows at or above its new threshold carries flag bit 0
+    (merge_packed leaves it uncertified).  ``tau1`` [nq] fp32 / ``pass0`` [nq, 4] int32 (pass-0 hit count,
+    r_eff, tightened, 0): optional outputs."""
+    _require_device(q, p, tau, packed)
+    ops.load().filter_passes_into(q, p, n_global, k, id_offset, tau, npasses, r, packed, tau1, pass0)
+
+
 def dist_filter_lists_into(q: torch.Tensor, p: torch.Tensor, n_global: int, k: int, id_offset: int,
                            lists: torch.Tensor, q0: int, packed: torch.Tensor) -> None:
     """dist_filter_lists for the query rows [q0, q0 + nq) of lists [nlists, NQ, r] gathered for a

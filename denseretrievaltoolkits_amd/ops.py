@@ -13,6 +13,7 @@ formula of the fused score + cross-entropy op.
     torch.ops.drt.ip_topk_large(_keys) / merge_exact    (k > 2048; sharded: merged by exact order keys)
     torch.ops.drt.dist_sample / dist_tau / dist_filter / dist_filter_chunks_into / dist_filter_lists / merge_packed
                                                                                             (sharded, §8e)
+    torch.ops.drt.filter_passes_into   (one GPU's group filter: interleaved passes, tightened threshold)
     torch.ops.drt.score_ce_fwd(q, p, stride, scale)     -> (loss, scores, lse)     biencoder.py:107-119
     torch.ops.drt.score_ce_bwd(g, q, p, scores, lse, stride, scale) -> (dq, dp)
     torch.ops.drt.embed_ln / linear / attention / layernorm / pool / l2_normalize  (BertModel pieces)
@@ -131,6 +132,10 @@ def _register_python_parts():
 
     @lib.register_fake("drt::dist_filter_chunks_into")
     def _(q, p, n_global, k, id_offset, tau, starts, packed):
+        return None
+
+    @lib.register_fake("drt::filter_passes_into")
+    def _(q, p, n_global, k, id_offset, tau, npasses, r, packed, tau1=None, pass0=None):
         return None
 
     @lib.register_fake("drt::dist_filter_lists_into")

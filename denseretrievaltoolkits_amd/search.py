@@ -121,6 +121,14 @@ GROUP_MIN_ROWS = 500_000
 # sharded index (round 5: 10M rows 1.90 vs 2.13 ms per batch, tools/group_chunk_probe.py,
 # profiles/r05g/; 1.25M rows is also the W = 8 shard).
 GROUP_CHUNK_ROWS = 1_250_000
+# One GPU: the group's launches are interleaved passes over the shard (launch p of P scans the 16-row tiles
+# t with t % P == p: the same rows per launch as a chunk, but a strided sample of the shard), and after the
+# first pass each query's threshold is raised to the r-th best score that pass collected -- an estimate of
+# the tail from 1 / P of the shard instead of the 62.5k-row sample, so the other P - 1 passes collect ~r
+# hits per query instead of ~512 (kernels.filter_passes_into; the select certifies the tightened lists).
+# False: contiguous chunks against the sample threshold (kernels.dist_filter_chunks_into), the form a
+# sharded index always takes (under a global threshold a shard's short list is normal).  Read per call.
+TIGHTEN_AFTER_FIRST_PASS = True
 
 
 def group_chunks(nrows: int, chunk_rows: int = None, nch: int = None):
@@ -207,8 +215,9 @@ def _gtau_enqueue_group(local, qs, k: int, n_global: int, offset: int, gather, t
     ``id_shift`` is added to every returned id (a one-GPU index searched with an id offset: the
     protocol itself runs on the index's own row numbers, packed in 32 bits).  ``chunks``: the filter runs as
     one launch per row range of this shard (group_chunks) and the chunks' hits are selected once
-    (kernels.dist_filter_chunks_into; d > 768: each chunk's packed lists are a part of the merge, gathered
-    [world, chunks, ...] -- the same chunk count on every rank).  ``side`` (a _SideChannel): everything
+    (kernels.dist_filter_chunks_into; on one GPU with TIGHTEN_AFTER_FIRST_PASS as many interleaved passes,
+    the later ones against a tightened threshold: kernels.filter_passes_into; d > 768: each chunk's packed
+    lists are a part of the merge, gathered [world, chunks, ...] -- the same chunk count on every rank).  ``side`` (a _SideChannel): everything
     after the filter scans -- exchange, merge, canonical stage, status staging -- goes on the side stream
     and through its communicator, so the caller can enqueue the next group's scans behind it."""
     sizes = [q.shape[0] for q in qs]
@@ -224,8 +233,12 @@ def _gtau_enqueue_group(local, qs, k: int, n_global: int, offset: int, gather, t
         # long shard: one filter launch per row chunk (the group's query blocks stay in step over a
         # chunk, so its tiles are read from HBM once), all chunks' hits in one list, one select
         lists = torch.empty((qg.shape[0], lc + 1), dtype=torch.int64, device=qg.device)
-        starts = [a for a, _ in chunks] + [chunks[-1][1]]
-        kernels.dist_filter_chunks_into(qg, local.rows, n_global, lc, offset, tau, starts, lists)
+        if TIGHTEN_AFTER_FIRST_PASS and world == 1 and offset == 0 and n_global == local.rows.shape[0]:
+            # one GPU: as many interleaved passes as chunks, the later ones against the tightened threshold
+            kernels.filter_passes_into(qg, local.rows, n_global, lc, offset, tau, len(chunks), lists)
+        else:
+            starts = [a for a, _ in chunks] + [chunks[-1][1]]
+            kernels.dist_filter_chunks_into(qg, local.rows, n_global, lc, offset, tau, starts, lists)
     elif chunks is not None and len(chunks) > 1:
         # (wider rows) one filter launch + select per chunk, every chunk's lists a part of the merge
         lists = torch.empty((len(chunks), qg.shape[0], kc + 1), dtype=torch.int64, device=qg.device)

@@ -222,6 +222,25 @@ int drt_ip_topk_dist_filter_chunks(const void* Q, int64_t nq, const void* P, int
                                    int64_t n_global, int32_t d, int32_t k, int64_t id_offset,
                                    const float* tau, uint64_t* packed, const int64_t* starts,
                                    int32_t nchunks, void* ws, size_t ws_bytes, void* stream);
+/* 4 over a shard that is the whole corpus as `npasses` interleaved passes (d <= 768, n_local < 2^32):
+ * pass p is one filter scan launch over the 16-row tiles t with t % npasses == p, all passes append to
+ * one hit list and one select emits the packed top-k.  Pass 0 filters against tau; each query's
+ * threshold is then raised to tau1 = the score of the r-th best key pass 0 collected (tau where it
+ * collected fewer than r, overflowed, or tau is NaN) and the later passes filter against tau1.
+ * r > 0: that rank; r < 0: drt_ip_topk_tighten_rank(n_local, npasses, k); r = 0: no tightening.
+ * Certificate: a tightened query (tau1 > tau) whose r_eff + (hits of passes 1..) is below k -- r_eff =
+ * pass-0 hits scoring >= tau1 -- gets flag bit 0, so drt_topk_merge_packed leaves it uncertified; every
+ * other list equals drt_ip_topk_dist_filter's over the whole shard.  tau1_out [nq] fp32 and pass0_out
+ * [nq][4] u32 (pass-0 hit count, r_eff, tightened, 0) are optional (NULL) copies for inspection.
+ * Workspace: drt_ip_topk_filter_passes_workspace.                                                    */
+int32_t drt_ip_topk_tighten_rank(int64_t n_local, int32_t npasses, int32_t k);
+size_t drt_ip_topk_filter_passes_workspace(int64_t nq, int64_t n_local, int64_t n_global, int32_t d,
+                                           int32_t k);
+int drt_ip_topk_filter_passes(const void* Q, int64_t nq, const void* P, int64_t n_local,
+                              int64_t n_global, int32_t d, int32_t k, int64_t id_offset,
+                              const float* tau, uint64_t* packed, int32_t npasses, int32_t r,
+                              float* tau1_out, uint32_t* pass0_out, void* ws, size_t ws_bytes,
+                              void* stream);
 /* 3+4 fused: tau from the gathered lists [nlists][nq][r] (written to tau_out when it is not
  * NULL) and this shard's packed top-k, with the hit counters zeroed by the threshold kernel
  * (3 launches).  Same results as drt_ip_topk_dist_tau followed by drt_ip_topk_dist_filter. */
