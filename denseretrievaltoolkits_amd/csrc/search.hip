@@ -5,20 +5,44 @@
 // filesystem shard exchange of Trainer._index_corpus/_load_index
 // (DRT/trainer/trainer.py:220-262).  Algorithm:
 //
-//   1. sample pass   ip_scan<DENSE> over a strided sample of M shard rows,
-//                    select<DENSE32,KTH> -> per-query threshold tau_q = r-th
-//                    largest sampled score (a lower bound of the k-th score
-//                    with probability 1 - 1e-9; certified in step 4).
-//   2. filter pass   ip_scan<FILTER> streams every shard row once from HBM
-//                    through LDS (global_load_lds, 3-deep ring), computes the
-//                    128-query x 32-row score tile with v_mfma_f32_32x32x16_bf16
-//                    (queries resident in VGPRs for the whole launch) and
-//                    appends (score, row) keys >= tau_q to a per-query list.
+//   1. sample pass   a strided sample of the shard's rows -> per-query threshold
+//                    tau_q = the r-th largest sampled score (a lower bound of
+//                    the k-th score with probability 1 - 1e-9; certified in
+//                    step 4).  One shard: ip_scan16_kernel<DENSE> writes every
+//                    sampled score, kth_rank / kth_partial + kth_final pick the
+//                    r-th.  Distributed and grouped (drt_ip_topk_dist_sample):
+//                    ip_scan16_kernel<TOPR> keeps each lane's best keys in
+//                    registers and kth_final takes the r-th of their union.
+//   2. filter pass   streams every shard row once from HBM through LDS
+//                    (global_load_lds into a ring of 16-row tiles, 5 slots at
+//                    d = 768), scores 16 rows x 16 queries per
+//                    v_mfma_f32_16x16x32_bf16 (queries resident in VGPRs for
+//                    the whole launch) and appends (score, row) keys >= tau_q
+//                    to a per-query list.  Kernels (launch_scan_d picks):
+//                    ip_scan16r_kernel, 16 queries per wave, the next tile's
+//                    fragment reads rolled into this tile's MFMAs (a launch of
+//                    up to 128 queries, d <= 768); ip_scan32r_kernel, 32 per
+//                    wave (more than 128 queries: a group of batches, whose
+//                    query blocks share each tile through L2);
+//                    ip_scan16_kernel<FILTER> for d > 768 or strided rows.
+//                    A group's filter over a large shard is several launches
+//                    into ONE hit list: row chunks
+//                    (drt_ip_topk_dist_filter_chunks) or interleaved passes,
+//                    tighten_kernel raising the threshold after the first
+//                    (drt_ip_topk_filter_passes).
 //   3. select        select<KEYS64,TOPK> per query: MSD radix select on the
 //                    64-bit key (score desc, row asc) + LDS bitonic sort.
 //   4. certify       count_q >= k (or == n) and count_q <= cap  <=> exact.
 //                    Otherwise status[q] = 1 and drt_ip_topk_resolve rescans
 //                    that query densely (exact by construction).
+//   5. canonical order (with row statistics): the refine kernels re-rank each
+//                    query's near-tie window by exact scores.
+// "Filter scan", "Canonical order", "One-GPU groups in row
+// chunks", "One-GPU groups as interleaved passes with a tightened threshold",
+// "Multi-GPU: global-threshold protocol".  The host side -- plans, the scan and
+// select launchers, the C entry points -- starts at "Host-side planning and
+// launch helpers"; the five filter entry points share the filter_* helpers
+// above drt_ip_topk_dist_filter.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -3459,6 +3483,10 @@ struct TopkPlan {
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Rows per query a threshold is set to let through over the whole corpus (the sample's r-th best score
+// stands for the target-th best of all rows); the hit lists hold 4x that (TopkPlan::cap).
+static int64_t hit_target(int64_t k) { return std::max<int64_t>(4096, 4 * k); }
+
 // Candidates the canonical-order stage selects per query: k plus a window for the entries within
 // 2 eps of the k-th score (a few on Gaussian data, <= 120 on the C2 leg's untrained-tower embeddings
 // at k = 1000, tools/c2_window_probe.py; up to 2048 in all).  A wider window goes to the wide resolve.
@@ -3496,7 +3524,7 @@ static TopkPlan make_plan(int64_t nq, int64_t n, int64_t k) {
   p.k = k;
   p.nq = nq;
   p.nq_pad = (nq + kQueriesPerWG - 1) / kQueriesPerWG * kQueriesPerWG;
-  const int64_t target = std::max<int64_t>(4096, 4 * k);  // expected hits per query
+  const int64_t target = hit_target(k);  // expected hits per query
   p.cap = 4 * target;
   if (n <= p.cap) {
     p.sample = false;
@@ -3549,7 +3577,7 @@ static TopkPlan make_dist_plan(int64_t nq, int64_t n_local, int64_t n_global, in
   p.k = k;
   p.nq = nq;
   p.nq_pad = g.nq_pad;
-  const int64_t target = std::max<int64_t>(4096, 4 * k);
+  const int64_t target = hit_target(k);
   p.cap = std::max<int64_t>(g.cap, 4 * target);
   p.sample = g.sample;
   p.r = g.sample ? g.r : 0;
@@ -3581,6 +3609,34 @@ static TopkPlan make_dist_plan(int64_t nq, int64_t n_local, int64_t n_global, in
   return p;
 }
 
+// ScanArgs::exp_hits of a filter launch under a distributed plan `p` of a corpus of n_global rows (it picks
+// the append flavour of the wide-row kernel, launch_scan_d).  Two forms, on purpose:
+// a launch over `rows` contiguous rows -- the whole shard, or one chunk of it -- expects that run's share
+// of the target (without a sample the threshold is -inf: every row hits) ...
+static int64_t rows_exp_hits(const TopkPlan& p, int64_t rows, int64_t n_global) {
+  return p.sample ? std::max<int64_t>(1, hit_target(p.k) * rows / std::max<int64_t>(1, n_global)) : rows;
+}
+
+// ... and one of `npasses` interleaved passes expects the shard's share divided by the passes.
+static int64_t pass_exp_hits(const TopkPlan& p, int64_t npasses, int64_t n_global) {
+  return p.sample ? std::max<int64_t>(1, hit_target(p.k) * p.n / npasses / std::max<int64_t>(1, n_global))
+                  : std::max<int64_t>(1, p.n / npasses);
+}
+
+// The part of ScanArgs every launch shares: dense [nq, d] queries and [*, d] corpus rows, addressed as one
+// contiguous run from P's first row.  nrows and the mode's outputs are the caller's.
+static ScanArgs scan_args(const void* Q, int64_t nq, const void* P, int32_t d) {
+  ScanArgs a{};
+  a.Q = (const __bf16*)Q;
+  a.nq = nq;
+  a.ldq = d;
+  a.P = (const __bf16*)P;
+  a.ldp = d;
+  a.row0 = 0;
+  a.rstride = 1;
+  return a;
+}
+
 static int scan_grid_x(int64_t ntiles) {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) {
@@ -3592,13 +3648,14 @@ static int scan_grid_x(int64_t ntiles) {
   return (int)std::max<int64_t>(g, 1);
 }
 
-// Grid of the 16-row scans (128 queries per work-group row): several 128-query blocks in one launch (a
-// group of batches) get gridDim.x = CUs / blocks, a multiple of 8, so work-groups (x, y) and (x, y') -- the
+// Grid of the 16-row scans (`qpw` queries per work-group row: 128, or 256 for the 32-queries-per-wave
+// filter kernel): several query blocks in one launch (a group of batches) get gridDim.x = CUs / blocks,
+// a multiple of 8, so work-groups (x, y) and (x, y') -- the
 // same tiles for different query blocks -- sit on the same XCD (work-groups are dealt to XCDs round-robin
 // by linear id) and run at the same time: a tile comes from HBM once and from that XCD's L2 for the other
 // blocks.  (gridDim.x = CUs ran the blocks one after another, each streaming the whole shard from HBM.)
-static dim3 scan16_grid(int64_t nq, int64_t nrows) {
-  const unsigned gy = (unsigned)((nq + kQueriesPerWG - 1) / kQueriesPerWG);
+static dim3 scan16_grid(int64_t nq, int64_t nrows, int qpw = kQueriesPerWG) {
+  const unsigned gy = (unsigned)((nq + qpw - 1) / qpw);
   const int64_t ntiles = (nrows + kT16 - 1) / kT16;
   int gx = scan_grid_x(ntiles);
   if (gy > 1 && ntiles >= 8) {
@@ -3613,7 +3670,8 @@ template <int D>
 static int launch_scan_d(const ScanArgs& a, int mode, hipStream_t s) {
   if (a.nq == 0 || a.nrows == 0) return DRT_OK;
   // an interleaved pass (the lean filter kernels only) is gridded over its own tiles
-  if (a.npass > 1 && (mode != SCAN_FILTER || D > 768 || a.row0 != 0 || a.rstride != 1 || a.pass < 0 ||
+  constexpr bool kLean = D <= 768;   // the lean filter kernels (ip_scan16r / ip_scan32r) exist for these rows
+  if (a.npass > 1 && (mode != SCAN_FILTER || !kLean || a.row0 != 0 || a.rstride != 1 || a.pass < 0 ||
                       a.pass >= a.npass))
     return DRT_EINVAL;
   const int64_t ntiles = pass_tiles((int)((a.nrows + kT16 - 1) / kT16), a.npass, a.pass);
@@ -3632,28 +3690,30 @@ static int launch_scan_d(const ScanArgs& a, int mode, hipStream_t s) {
     const bool dense_hits = eh * 256.0 / (double)a.nrows >= 0.35;
     // d > 768: the rolled reads hold two tiles' fragments beside the queries' (2 x d / 32 x 4 VGPRs +
     // d / 32 x 4): that spills from d = 832, so wider rows take the same loop with the fragments read
-    // per k-step (ip_scan16_kernel: same MFMA order, identical results)
+    // per k-step (ip_scan16_kernel: same MFMA order, identical results), and the lean kernels are
+    // instantiated for d <= 768 only (ip_scan32r's 32 queries' fragments spill from d = 832 as well)
     // (ip_scan16r addresses rows as one contiguous run: row0 0, rstride 1 -- every filter pass)
-    if (D > 768 || a.row0 != 0 || a.rstride != 1) {
+    bool lean = false;
+    if constexpr (kLean) {
+      lean = a.row0 == 0 && a.rstride == 1;
+      if (lean) {
+        // non-temporal corpus loads for a single block; a group's blocks share each tile through L2, and a
+        // group of more than 128 queries takes the 32-queries-per-wave kernel (256 per work-group)
+        if (gy > 1) {
+          const dim3 grid32 = scan16_grid(a.nq, ntiles * kT16, kQueriesPerWG32);
+          hipLaunchKernelGGL((ip_scan32r_kernel<D>), grid32, dim3(512), 0, s, a);
+        } else if (gy > 1) {
+          // not reached since the 32-query kernel took every launch of several blocks; dropping this arm
+          // takes the twelve ip_scan16r_kernel<D, false> out of the code object: a change of its own
+          hipLaunchKernelGGL((ip_scan16r_kernel<D, false>), grid, dim3(512), 0, s, a);
+        } else {
+          hipLaunchKernelGGL((ip_scan16r_kernel<D, true>), grid, dim3(512), 0, s, a);
+        }
+      }
+    }
+    if (!lean) {
       if (dense_hits) hipLaunchKernelGGL((ip_scan16_kernel<D, SCAN_FILTER, 8, true>), grid, dim3(512), 0, s, a);
       else hipLaunchKernelGGL((ip_scan16_kernel<D, SCAN_FILTER, 8, false>), grid, dim3(512), 0, s, a);
-    } else {
-      // non-temporal corpus loads for a single block; a group's blocks share each tile through L2, and a
-      // group of more than 128 queries takes the 32-queries-per-wave kernel (256 per work-group)
-      if (D <= 768 && gy > 1) {   // (wider rows: the 32 queries' fragments spill)
-        const unsigned gy32 = (unsigned)((a.nq + kQueriesPerWG32 - 1) / kQueriesPerWG32);
-        int gx32 = scan_grid_x(ntiles);
-        if (gy32 > 1 && ntiles >= 8) {
-          const int cus = scan_grid_x((int64_t)1 << 40);
-          const int share = std::max(8, (cus / (int)gy32) & ~7);
-          gx32 = (int)std::min<int64_t>(ntiles, share);
-        }
-        hipLaunchKernelGGL((ip_scan32r_kernel<D <= 768 ? D : 768>), dim3(gx32, gy32), dim3(512), 0, s, a);
-      } else if (gy > 1) {
-        hipLaunchKernelGGL((ip_scan16r_kernel<D, false>), grid, dim3(512), 0, s, a);
-      } else {
-        hipLaunchKernelGGL((ip_scan16r_kernel<D, true>), grid, dim3(512), 0, s, a);
-      }
     }
   } else if (mode == SCAN_TOPR) {
     hipLaunchKernelGGL((ip_scan16_kernel<D, SCAN_TOPR>), grid, dim3(512), 0, s, a);
@@ -3806,18 +3866,10 @@ static int ip_topk_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
   }
   DRT_REQUIRE(P != nullptr);
 
-  ScanArgs a{};
-  a.Q = (const __bf16*)Q;
-  a.nq = nq;
-  a.ldq = d;
-  a.P = (const __bf16*)P;
-  a.ldp = d;
-
   if (!p.sample) {
     // Small shard: score every row densely, select directly.
-    a.row0 = 0;
+    ScanArgs a = scan_args(Q, nq, P, d);
     a.nrows = n;
-    a.rstride = 1;
     a.out = w + p.off_keys;
     a.cap = p.cap;
     int rc = launch_scan(a, d, SCAN_DENSE, s, PROF_SCAN);
@@ -3832,13 +3884,14 @@ static int ip_topk_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
     return launch_refine(ra, s);
   }
 
-  // 1. sample pass -> tau
-  a.row0 = p.stride / 2;
-  a.nrows = p.m;
-  a.rstride = p.stride;
-  a.out = w + p.off_sample;
-  a.cap = align_up(p.m, 4);
-  int rc = launch_scan(a, d, SCAN_DENSE, s, PROF_SAMPLE);
+  // 1. sample pass -> tau: every stride-th row, densely scored
+  ScanArgs smp_a = scan_args(Q, nq, P, d);
+  smp_a.row0 = p.stride / 2;
+  smp_a.nrows = p.m;
+  smp_a.rstride = p.stride;
+  smp_a.out = w + p.off_sample;
+  smp_a.cap = align_up(p.m, 4);
+  int rc = launch_scan(smp_a, d, SCAN_DENSE, s, PROF_SAMPLE);
   if (rc) return rc;
   {
     const ProfPair pp = prof_begin(PROF_SELECT, s);
@@ -3868,9 +3921,8 @@ static int ip_topk_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
   }
 
   // 2. filter pass (counters zeroed by the threshold kernel above: one launch fewer than a memset)
-  a.row0 = 0;
+  ScanArgs a = scan_args(Q, nq, P, d);
   a.nrows = n;
-  a.rstride = 1;
   a.tau = tau;
   a.counts = cnt;
   a.out = w + p.off_keys;
@@ -4066,15 +4118,8 @@ static int resolve_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
       rc = (int)e;
       break;
     }
-    ScanArgs a{};
-    a.Q = (const __bf16*)qbuf;
-    a.nq = nb;
-    a.ldq = d;
-    a.P = (const __bf16*)P;
-    a.ldp = d;
-    a.row0 = 0;
+    ScanArgs a = scan_args(qbuf, nb, P, d);
     a.nrows = n;
-    a.rstride = 1;
     a.out = sbuf;
     a.cap = width;
     rc = launch_scan(a, d, SCAN_DENSE, s, -1);
@@ -4196,15 +4241,8 @@ int drt_ip_topk_resolve_wide(const void* Q, int64_t nq, const void* P, int64_t n
     w.status = status;
     hipLaunchKernelGGL(wide_prep_kernel, dim3((unsigned)B), dim3(kRefThreads), 0, s, w);
     DRT_CHECK_HIP(hipGetLastError());
-    ScanArgs a{};
-    a.Q = (const __bf16*)qbuf;
-    a.nq = nb;
-    a.ldq = d;
-    a.P = (const __bf16*)P;
-    a.ldp = d;
-    a.row0 = 0;
+    ScanArgs a = scan_args(qbuf, nb, P, d);
     a.nrows = n;
-    a.rstride = 1;
     a.tau = tau;
     a.counts = counts;
     a.out = keys;
@@ -4293,15 +4331,8 @@ int drt_ip_topk_large_keys(const void* Q, int64_t nq, const void* P, int64_t n, 
     hipLaunchKernelGGL(wide_prep_kernel, dim3((unsigned)B), dim3(kRefThreads), 0, s, w);
     DRT_CHECK_HIP(hipGetLastError());
     if (n > 0) {
-      ScanArgs a{};
-      a.Q = w.ra.Q;
-      a.nq = nb;
-      a.ldq = d;
-      a.P = (const __bf16*)P;
-      a.ldp = d;
-      a.row0 = 0;
+      ScanArgs a = scan_args(w.ra.Q, nb, P, d);
       a.nrows = n;
-      a.rstride = 1;
       a.tau = tauc;
       a.counts = counts;
       a.out = keys;
@@ -4392,12 +4423,7 @@ int drt_ip_topk_dist_sample(const void* Q, int64_t nq, const void* P, int64_t n_
   }
   DRT_REQUIRE(P != nullptr);
   char* w = (char*)ws;
-  ScanArgs a{};
-  a.Q = (const __bf16*)Q;
-  a.nq = nq;
-  a.ldq = d;
-  a.P = (const __bf16*)P;
-  a.ldp = d;
+  ScanArgs a = scan_args(Q, nq, P, d);
   a.row0 = p.stride / 2;
   a.nrows = p.m;
   a.rstride = p.stride;
@@ -4443,54 +4469,84 @@ int drt_ip_topk_dist_tau(const uint32_t* lists, int64_t nq, int32_t nlists, int3
   return hip_status(hipGetLastError());
 }
 
-int drt_ip_topk_dist_filter(const void* Q, int64_t nq, const void* P, int64_t n_local, int64_t n_global, int32_t d,
-                            int32_t k, int64_t id_offset, const float* tau, uint64_t* packed, void* ws,
-                            size_t ws_bytes, void* stream) {
+// The filter step: scan the shard against a threshold per query, one select over the hits.  The five entry
+// points below differ in where the threshold comes from and in how the shard is cut into scan launches,
+// and share the rest through four helpers, called in this order:
+//   filter_setup    every check that precedes the first HIP call, the plan, the select's arguments and
+//                   the ScanArgs of one launch over the whole shard
+//   (the entry's own work before the scan: the fused form's threshold kernel, the passes' copies)
+//   filter_begin    a non-empty shard only: the corpus pointer check, the hit counters zeroed
+//   launch_scan     once per launch the entry wants: a copy of FilterRun::scan with that launch's
+//                   threshold, rows and exp_hits (rows_exp_hits / pass_exp_hits above)
+//   filter_select   the select over the hit lists, or over nothing for an empty shard
+struct FilterRun {
+  TopkPlan p;
+  hipStream_t s;
+  char* w;         // the workspace
+  uint32_t* cnt;   // the hit counters in it
+  SelectArgs sel;
+  ScanArgs scan;
+};
+
+// `thr` is the entry's threshold source (tau, or the sample lists).  DRT_OK with nq == 0: nothing to do.
+static int filter_setup(FilterRun& f, const void* Q, int64_t nq, const void* P, int64_t n_local, int64_t n_global,
+                        int32_t d, int32_t k, int64_t id_offset, const void* thr, uint64_t* packed, void* ws,
+                        size_t ws_bytes, void* stream) {
   DRT_REQUIRE(valid_dist_dims(nq, n_local, n_global, d, k));
   DRT_REQUIRE(id_offset >= 0 && id_offset + n_local <= n_global);
   if (nq == 0) return DRT_OK;
-  DRT_REQUIRE(Q && tau && packed && ws);
-  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
-  DRT_REQUIRE(ws_bytes >= p.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  uint32_t* cnt = (uint32_t*)(w + p.off_cnt);
-  SelectArgs sa{};
-  sa.in = w + p.off_keys;
-  sa.in_stride = p.cap;
-  sa.k = k;
-  sa.nq = nq;
-  sa.id_offset = id_offset;
-  sa.out_packed = packed;
-  sa.global_tau = true;
-  if (n_local == 0) {
-    sa.n_in = 0;
-    sa.n_total = 0;
-    return launch_select(sa, SEL_DENSE32, SEL_TOPK, s);
+  DRT_REQUIRE(Q && thr && packed && ws);
+  f.p = make_dist_plan(nq, n_local, n_global, k);
+  DRT_REQUIRE(ws_bytes >= f.p.total);
+  f.s = (hipStream_t)stream;
+  f.w = (char*)ws;
+  f.cnt = (uint32_t*)(f.w + f.p.off_cnt);
+  f.sel = SelectArgs{};
+  f.sel.in = f.w + f.p.off_keys;
+  f.sel.in_stride = f.p.cap;
+  f.sel.k = k;
+  f.sel.nq = nq;
+  f.sel.id_offset = id_offset;
+  f.sel.out_packed = packed;
+  f.sel.global_tau = true;
+  f.scan = scan_args(Q, nq, P, d);
+  f.scan.nrows = n_local;
+  f.scan.counts = f.cnt;
+  f.scan.out = f.w + f.p.off_keys;
+  f.scan.cap = f.p.cap;
+  return DRT_OK;
+}
+
+// zero_counts false: the entry's threshold kernel has zeroed the counters (one launch fewer)
+static int filter_begin(const FilterRun& f, bool zero_counts) {
+  DRT_REQUIRE(f.scan.P != nullptr);
+  if (zero_counts) DRT_CHECK_HIP(hipMemsetAsync(f.cnt, 0, f.p.nq_pad * 4 * kCntStride, f.s));
+  return DRT_OK;
+}
+
+static int filter_select(FilterRun& f) {
+  if (f.p.n == 0) return launch_select(f.sel, SEL_DENSE32, SEL_TOPK, f.s);   // n_in = n_total = 0: empty lists
+  f.sel.counts = f.cnt;
+  f.sel.cap = f.p.cap;
+  f.sel.n_total = f.p.n;
+  return launch_select(f.sel, SEL_KEYS64, SEL_TOPK, f.s);
+}
+
+// One launch over the whole shard.
+int drt_ip_topk_dist_filter(const void* Q, int64_t nq, const void* P, int64_t n_local, int64_t n_global, int32_t d,
+                            int32_t k, int64_t id_offset, const float* tau, uint64_t* packed, void* ws,
+                            size_t ws_bytes, void* stream) {
+  FilterRun f;
+  int rc = filter_setup(f, Q, nq, P, n_local, n_global, d, k, id_offset, tau, packed, ws, ws_bytes, stream);
+  if (rc || nq == 0) return rc;
+  if (n_local > 0) {
+    if ((rc = filter_begin(f, true))) return rc;
+    ScanArgs a = f.scan;
+    a.tau = tau;
+    a.exp_hits = rows_exp_hits(f.p, n_local, n_global);
+    if ((rc = launch_scan(a, d, SCAN_FILTER, f.s, PROF_SCAN))) return rc;
   }
-  DRT_REQUIRE(P != nullptr);
-  DRT_CHECK_HIP(hipMemsetAsync(cnt, 0, p.nq_pad * 4 * kCntStride, s));
-  ScanArgs a{};
-  a.Q = (const __bf16*)Q;
-  a.nq = nq;
-  a.ldq = d;
-  a.P = (const __bf16*)P;
-  a.ldp = d;
-  a.row0 = 0;
-  a.nrows = n_local;
-  a.rstride = 1;
-  a.tau = tau;
-  a.counts = cnt;
-  a.out = w + p.off_keys;
-  a.cap = p.cap;
-  const int64_t target = std::max<int64_t>(4096, 4 * (int64_t)k);
-  a.exp_hits = p.sample ? std::max<int64_t>(1, target * n_local / std::max<int64_t>(1, n_global)) : n_local;
-  int rc = launch_scan(a, d, SCAN_FILTER, s, PROF_SCAN);
-  if (rc) return rc;
-  sa.counts = cnt;
-  sa.cap = p.cap;
-  sa.n_total = n_local;
-  return launch_select(sa, SEL_KEYS64, SEL_TOPK, s);
+  return filter_select(f);
 }
 
 // dist_filter over a shard in row chunks with ONE hit list and ONE select: chunk c = rows
@@ -4503,59 +4559,27 @@ int drt_ip_topk_dist_filter(const void* Q, int64_t nq, const void* P, int64_t n_
 int drt_ip_topk_dist_filter_chunks(const void* Q, int64_t nq, const void* P, int64_t n_local, int64_t n_global,
                                    int32_t d, int32_t k, int64_t id_offset, const float* tau, uint64_t* packed,
                                    const int64_t* starts, int32_t nchunks, void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(valid_dist_dims(nq, n_local, n_global, d, k));
-  DRT_REQUIRE(id_offset >= 0 && id_offset + n_local <= n_global);
   DRT_REQUIRE(d <= 768 && n_local < ((int64_t)1 << 32));
   DRT_REQUIRE(starts != nullptr && nchunks >= 1 && starts[0] == 0 && starts[nchunks] == n_local);
   for (int c = 0; c < nchunks; ++c) DRT_REQUIRE(starts[c] <= starts[c + 1]);
-  if (nq == 0) return DRT_OK;
-  DRT_REQUIRE(Q && tau && packed && ws);
-  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
-  DRT_REQUIRE(ws_bytes >= p.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  uint32_t* cnt = (uint32_t*)(w + p.off_cnt);
-  SelectArgs sa{};
-  sa.in = w + p.off_keys;
-  sa.in_stride = p.cap;
-  sa.k = k;
-  sa.nq = nq;
-  sa.id_offset = id_offset;
-  sa.out_packed = packed;
-  sa.global_tau = true;
-  if (n_local == 0) {
-    sa.n_in = 0;
-    sa.n_total = 0;
-    return launch_select(sa, SEL_DENSE32, SEL_TOPK, s);
+  FilterRun f;
+  int rc = filter_setup(f, Q, nq, P, n_local, n_global, d, k, id_offset, tau, packed, ws, ws_bytes, stream);
+  if (rc || nq == 0) return rc;
+  if (n_local > 0) {
+    if ((rc = filter_begin(f, true))) return rc;
+    for (int c = 0; c < nchunks; ++c) {
+      const int64_t r0 = starts[c], rows = starts[c + 1] - starts[c];
+      if (rows == 0) continue;
+      ScanArgs a = f.scan;
+      a.P += r0 * d;
+      a.nrows = rows;
+      a.row_base = (uint32_t)r0;
+      a.tau = tau;
+      a.exp_hits = rows_exp_hits(f.p, rows, n_global);   // the chunk's rows, not the shard's
+      if ((rc = launch_scan(a, d, SCAN_FILTER, f.s, PROF_SCAN))) return rc;
+    }
   }
-  DRT_REQUIRE(P != nullptr);
-  DRT_CHECK_HIP(hipMemsetAsync(cnt, 0, p.nq_pad * 4 * kCntStride, s));
-  const int64_t target = std::max<int64_t>(4096, 4 * (int64_t)k);
-  for (int c = 0; c < nchunks; ++c) {
-    const int64_t r0 = starts[c], rows = starts[c + 1] - starts[c];
-    if (rows == 0) continue;
-    ScanArgs a{};
-    a.Q = (const __bf16*)Q;
-    a.nq = nq;
-    a.ldq = d;
-    a.P = (const __bf16*)P + r0 * d;
-    a.ldp = d;
-    a.row0 = 0;
-    a.nrows = rows;
-    a.rstride = 1;
-    a.tau = tau;
-    a.counts = cnt;
-    a.out = w + p.off_keys;
-    a.cap = p.cap;
-    a.exp_hits = p.sample ? std::max<int64_t>(1, target * rows / std::max<int64_t>(1, n_global)) : rows;
-    a.row_base = (uint32_t)r0;
-    const int rc = launch_scan(a, d, SCAN_FILTER, s, PROF_SCAN);
-    if (rc) return rc;
-  }
-  sa.counts = cnt;
-  sa.cap = p.cap;
-  sa.n_total = n_local;
-  return launch_select(sa, SEL_KEYS64, SEL_TOPK, s);
+  return filter_select(f);
 }
 
 // Rank of the tightened threshold (drt_ip_topk_filter_passes): with C = shard tiles / first-pass tiles, the
@@ -4576,10 +4600,13 @@ int32_t drt_ip_topk_tighten_rank(int64_t n_local, int32_t npasses, int32_t k) {
   return 0;
 }
 
+// The distributed workspace plus [nq_pad][4] u32 of pass-0 state.
+static size_t passes_pass0_offset(const TopkPlan& p) { return align_up(p.total, 256); }
+static size_t passes_ws_bytes(const TopkPlan& p) { return passes_pass0_offset(p) + (size_t)p.nq_pad * 16; }
+
 size_t drt_ip_topk_filter_passes_workspace(int64_t nq, int64_t n_local, int64_t n_global, int32_t d, int32_t k) {
   if (!valid_dist_dims(nq, n_local, n_global, d, k)) return 0;
-  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
-  return align_up(p.total, 256) + (size_t)p.nq_pad * 16;
+  return passes_ws_bytes(make_dist_plan(nq, n_local, n_global, k));
 }
 
 // dist_filter over a shard as `npasses` interleaved passes with ONE hit list and ONE select: pass p is
@@ -4598,76 +4625,41 @@ int drt_ip_topk_filter_passes(const void* Q, int64_t nq, const void* P, int64_t 
                               int32_t d, int32_t k, int64_t id_offset, const float* tau, uint64_t* packed,
                               int32_t npasses, int32_t r, float* tau1_out, uint32_t* pass0_out, void* ws,
                               size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(valid_dist_dims(nq, n_local, n_global, d, k));
-  DRT_REQUIRE(id_offset >= 0 && id_offset + n_local <= n_global);
   DRT_REQUIRE(d <= 768 && n_local < ((int64_t)1 << 32) && npasses >= 1 && npasses <= 1024);
-  if (nq == 0) return DRT_OK;
-  DRT_REQUIRE(Q && tau && packed && ws);
-  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
-  const size_t off_pass0 = align_up(p.total, 256);
-  DRT_REQUIRE(ws_bytes >= off_pass0 + (size_t)p.nq_pad * 16);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  uint32_t* cnt = (uint32_t*)(w + p.off_cnt);
-  SelectArgs sa{};
-  sa.in = w + p.off_keys;
-  sa.in_stride = p.cap;
-  sa.k = k;
-  sa.nq = nq;
-  sa.id_offset = id_offset;
-  sa.out_packed = packed;
-  sa.global_tau = true;
+  FilterRun f;
+  int rc = filter_setup(f, Q, nq, P, n_local, n_global, d, k, id_offset, tau, packed, ws, ws_bytes, stream);
+  if (rc || nq == 0) return rc;
+  DRT_REQUIRE(ws_bytes >= passes_ws_bytes(f.p));
   if (r < 0) r = drt_ip_topk_tighten_rank(n_local, npasses, k);
   const int tall = (int)((n_local + kT16 - 1) / kT16);
   const bool tighten = r > 0 && n_local > 0 && pass_tiles(tall, npasses, 0) < tall;
   if (!tighten) {
-    if (tau1_out) DRT_CHECK_HIP(hipMemcpyAsync(tau1_out, tau, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
-    if (pass0_out) DRT_CHECK_HIP(hipMemsetAsync(pass0_out, 0, (size_t)nq * 16, s));
+    if (tau1_out) DRT_CHECK_HIP(hipMemcpyAsync(tau1_out, tau, (size_t)nq * 4, hipMemcpyDeviceToDevice, f.s));
+    if (pass0_out) DRT_CHECK_HIP(hipMemsetAsync(pass0_out, 0, (size_t)nq * 16, f.s));
   }
-  if (n_local == 0) {
-    sa.n_in = 0;
-    sa.n_total = 0;
-    return launch_select(sa, SEL_DENSE32, SEL_TOPK, s);
-  }
-  DRT_REQUIRE(P != nullptr);
-  DRT_CHECK_HIP(hipMemsetAsync(cnt, 0, p.nq_pad * 4 * kCntStride, s));
-  float* tau1 = tau1_out ? tau1_out : (float*)(w + p.off_tau);
-  uint32_t* pass0 = pass0_out ? pass0_out : (uint32_t*)(w + off_pass0);
-  const int64_t target = std::max<int64_t>(4096, 4 * (int64_t)k);
-  for (int ps = 0; ps < npasses; ++ps) {
-    if (pass_tiles(tall, npasses, ps) == 0) continue;
-    ScanArgs a{};
-    a.Q = (const __bf16*)Q;
-    a.nq = nq;
-    a.ldq = d;
-    a.P = (const __bf16*)P;
-    a.ldp = d;
-    a.row0 = 0;
-    a.nrows = n_local;
-    a.rstride = 1;
-    a.tau = (tighten && ps > 0) ? tau1 : tau;
-    a.counts = cnt;
-    a.out = w + p.off_keys;
-    a.cap = p.cap;
-    a.exp_hits = p.sample ? std::max<int64_t>(1, target * n_local / npasses / std::max<int64_t>(1, n_global))
-                          : std::max<int64_t>(1, n_local / npasses);
-    a.npass = npasses;
-    a.pass = ps;
-    const int rc = launch_scan(a, d, SCAN_FILTER, s, PROF_SCAN);
-    if (rc) return rc;
-    if (tighten && ps == 0) {
-      const ProfPair pp = prof_begin(PROF_SELECT, s);
-      hipLaunchKernelGGL(tighten_kernel, dim3((unsigned)nq), dim3(kTightThreads), 0, s,
-                         (const uint64_t*)(w + p.off_keys), p.cap, (const uint32_t*)cnt, tau, (int)r, tau1, pass0);
-      prof_end(pp, s);
-      DRT_CHECK_HIP(hipGetLastError());
+  float* tau1 = tau1_out ? tau1_out : (float*)(f.w + f.p.off_tau);
+  uint32_t* pass0 = pass0_out ? pass0_out : (uint32_t*)(f.w + passes_pass0_offset(f.p));
+  if (n_local > 0) {
+    if ((rc = filter_begin(f, true))) return rc;
+    for (int ps = 0; ps < npasses; ++ps) {
+      if (pass_tiles(tall, npasses, ps) == 0) continue;
+      ScanArgs a = f.scan;
+      a.npass = npasses;
+      a.pass = ps;
+      a.tau = (tighten && ps > 0) ? tau1 : tau;
+      a.exp_hits = pass_exp_hits(f.p, npasses, n_global);   // the shard's share over the passes
+      if ((rc = launch_scan(a, d, SCAN_FILTER, f.s, PROF_SCAN))) return rc;
+      if (tighten && ps == 0) {
+        const ProfPair pp = prof_begin(PROF_SELECT, f.s);
+        hipLaunchKernelGGL(tighten_kernel, dim3((unsigned)nq), dim3(kTightThreads), 0, f.s,
+                           (const uint64_t*)f.scan.out, f.p.cap, (const uint32_t*)f.cnt, tau, (int)r, tau1, pass0);
+        prof_end(pp, f.s);
+        DRT_CHECK_HIP(hipGetLastError());
+      }
     }
   }
-  sa.counts = cnt;
-  sa.cap = p.cap;
-  sa.n_total = n_local;
-  sa.pass0 = tighten ? pass0 : nullptr;
-  return launch_select(sa, SEL_KEYS64, SEL_TOPK, s);
+  f.sel.pass0 = tighten ? pass0 : nullptr;
+  return filter_select(f);
 }
 
 // dist_tau + dist_filter in one call: the threshold kernel also zeroes the hit counters,
@@ -4686,58 +4678,35 @@ int drt_ip_topk_dist_filter_lists_at(const void* Q, int64_t nq, const void* P, i
                                      int32_t d, int32_t k, int64_t id_offset, const uint32_t* lists, int32_t nlists,
                                      int64_t lists_stride, float* tau_out, uint64_t* packed, void* ws,
                                      size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(valid_dist_dims(nq, n_local, n_global, d, k));
-  DRT_REQUIRE(id_offset >= 0 && id_offset + n_local <= n_global);
   const int32_t r = drt_ip_topk_sample_rank(k);
   DRT_REQUIRE(r > 0 && nlists >= 1 && (int64_t)nlists * r <= kKthChunk);
   DRT_REQUIRE(nlists == 1 || lists_stride >= nq * r);
-  if (nq == 0) return DRT_OK;
-  DRT_REQUIRE(Q && lists && packed && ws);
-  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
-  DRT_REQUIRE(ws_bytes >= p.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  uint32_t* cnt = (uint32_t*)(w + p.off_cnt);
-  float* tau = tau_out ? tau_out : (float*)(w + p.off_tau);
-  hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, s, lists, (int)nlists, (int)r,
-                     lists_stride, (int64_t)r, tau, (uint32_t*)nullptr, n_local > 0 ? cnt : (uint32_t*)nullptr,
+  FilterRun f;
+  int rc = filter_setup(f, Q, nq, P, n_local, n_global, d, k, id_offset, lists, packed, ws, ws_bytes, stream);
+  if (rc || nq == 0) return rc;
+  float* tau = tau_out ? tau_out : (float*)(f.w + f.p.off_tau);
+  hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, f.s, lists, (int)nlists, (int)r,
+                     lists_stride, (int64_t)r, tau, (uint32_t*)nullptr, n_local > 0 ? f.cnt : (uint32_t*)nullptr,
                      (int)r);
   DRT_CHECK_HIP(hipGetLastError());
-  SelectArgs sa{};
-  sa.in = w + p.off_keys;
-  sa.in_stride = p.cap;
-  sa.k = k;
-  sa.nq = nq;
-  sa.id_offset = id_offset;
-  sa.out_packed = packed;
-  sa.global_tau = true;
-  if (n_local == 0) {
-    sa.n_in = 0;
-    sa.n_total = 0;
-    return launch_select(sa, SEL_DENSE32, SEL_TOPK, s);
+  if (n_local > 0) {
+    if ((rc = filter_begin(f, false))) return rc;   // counters zeroed by the threshold kernel: no memset
+    ScanArgs a = f.scan;
+    a.tau = tau;
+    a.exp_hits = rows_exp_hits(f.p, n_local, n_global);
+    if ((rc = launch_scan(a, d, SCAN_FILTER, f.s, PROF_SCAN))) return rc;
   }
-  DRT_REQUIRE(P != nullptr);
-  ScanArgs a{};
-  a.Q = (const __bf16*)Q;
-  a.nq = nq;
-  a.ldq = d;
-  a.P = (const __bf16*)P;
-  a.ldp = d;
-  a.row0 = 0;
-  a.nrows = n_local;
-  a.rstride = 1;
-  a.tau = tau;
-  a.counts = cnt;
-  a.out = w + p.off_keys;
-  a.cap = p.cap;
-  const int64_t target = std::max<int64_t>(4096, 4 * (int64_t)k);
-  a.exp_hits = p.sample ? std::max<int64_t>(1, target * n_local / std::max<int64_t>(1, n_global)) : n_local;
-  int rc = launch_scan(a, d, SCAN_FILTER, s, PROF_SCAN);
-  if (rc) return rc;
-  sa.counts = cnt;
-  sa.cap = p.cap;
-  sa.n_total = n_local;
-  return launch_select(sa, SEL_KEYS64, SEL_TOPK, s);
+  return filter_select(f);
+}
+
+// merge_packed_count_kernel's dynamic LDS goes up to kCntMaxKeys keys: raised once, before its first launch.
+static hipError_t merge_count_lds_attr() {
+  static bool attr_set = false;
+  if (attr_set) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)merge_packed_count_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, kCntMaxKeys * 8);
+  attr_set = e == hipSuccess;
+  return e;
 }
 
 int drt_topk_merge_packed(const uint64_t* parts, int64_t nq, int32_t nparts, int32_t k, int64_t n_global,
@@ -4756,12 +4725,7 @@ int drt_topk_merge_packed_capped(const uint64_t* parts, int64_t nq, int32_t npar
   if (nq == 0) return DRT_OK;
   DRT_REQUIRE(parts && out_scores && out_ids);
   hipStream_t s = (hipStream_t)stream;
-  static bool attr_set = false;
-  if (!attr_set) {
-    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)merge_packed_count_kernel,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kCntMaxKeys * 8));
-    attr_set = true;
-  }
+  DRT_CHECK_HIP(merge_count_lds_attr());
   const ProfPair pp = prof_begin(PROF_MERGE, s);
   hipLaunchKernelGGL(merge_packed_count_kernel, dim3((unsigned)nq), dim3(kCntThreads), (size_t)nparts * lcap * 8, s,
                      parts, nq, (int)nparts, (int)k, n_global, out_scores, out_ids, status, (int)k_cert, (int)lcap);
@@ -4788,12 +4752,7 @@ int drt_topk_merge_packed_cert(const uint64_t* parts, int64_t nq, int32_t nparts
   const bool count_ok = nparts <= kCntMaxParts && (int64_t)nparts * k <= kCntMaxKeys;
   // one part (one GPU): the plain per-query kernel (tools/merge_bench.py: 8 vs 23 us at 2048 queries)
   if (count_ok && nparts > 1) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      DRT_CHECK_HIP(hipFuncSetAttribute((const void*)merge_packed_count_kernel,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kCntMaxKeys * 8));
-      attr_set = true;
-    }
+    DRT_CHECK_HIP(merge_count_lds_attr());
     hipLaunchKernelGGL(merge_packed_count_kernel, dim3((unsigned)nq), dim3(kCntThreads), cnt_lds, s, parts, nq,
                        (int)nparts, (int)k, n_global, out_scores, out_ids, status, (int)k_cert, (int)k);
   } else if (nparts > 1 && (p2 / 2) * kp <= kTreeMaxE * kTreeThreads && lds <= 128 * 1024) {

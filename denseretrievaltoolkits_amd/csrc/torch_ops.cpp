@@ -331,8 +331,10 @@ std::tuple<Tensor, Tensor> topk_merge(const Tensor& scores_, const Tensor& ids_,
   return {os, oi};
 }
 
-Tensor dist_ws(const Tensor& q, int64_t n_local, int64_t n_global, int64_t k, size_t* wsb) {
-  *wsb = drt_ip_topk_dist_workspace(q.size(0), n_local, n_global, (int32_t)q.size(1), (int32_t)k);
+// the distributed workspace; passes: that of drt_ip_topk_filter_passes (the same plus the pass-0 state)
+Tensor dist_ws(const Tensor& q, int64_t n_local, int64_t n_global, int64_t k, size_t* wsb, bool passes = false) {
+  *wsb = (passes ? drt_ip_topk_filter_passes_workspace
+                 : drt_ip_topk_dist_workspace)(q.size(0), n_local, n_global, (int32_t)q.size(1), (int32_t)k);
   TORCH_CHECK_VALUE(*wsb > 0 || q.size(0) == 0, "unsupported dist shape nq=", q.size(0), " n_local=", n_local,
               " n_global=", n_global, " d=", q.size(1), " k=", k);
   return workspace(q, *wsb);
@@ -366,88 +368,70 @@ Tensor dist_tau(const Tensor& lists_, int64_t k) {
   return tau;
 }
 
-Tensor dist_filter(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
-                   const Tensor& tau_) {
-  need(q_, "q", at::kBFloat16, 2);
-  need(p_, "p", at::kBFloat16, 2);
-  need(tau_, "tau", at::kFloat, 1);
-  const c10::DeviceGuard g(q_.device());
-  const Tensor q = q_.contiguous(), p = p_.contiguous(), tau = tau_.contiguous();
-  Tensor packed = at::empty({q.size(0), k + 1}, q.options().dtype(at::kLong));
+// What the filter wrappers share: the checks of q, p, the threshold source (tau [nq] fp32, or the sample
+// lists [nlists, NQ, r] int32, whose layout the caller checks) and the caller's packed [nq, k + 1] buffer;
+// the device guard, held while the object lives; contiguous inputs; the workspace.
+struct FilterPrelude {
+  c10::OptionalDeviceGuard guard;
+  Tensor q, p, thr, ws;
   size_t wsb = 0;
-  Tensor ws = dist_ws(q, p.size(0), n_global, k, &wsb);
-  check_rc(drt_ip_topk_dist_filter(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0), n_global,
-                                   (int32_t)q.size(1), (int32_t)k, id_offset, tau.data_ptr<float>(),
-                                   (uint64_t*)packed.data_ptr<int64_t>(), ws.data_ptr(), wsb, stream_of(q)),
-           "drt_ip_topk_dist_filter");
-  return packed;
-}
+  int64_t n_global, k;
 
-Tensor dist_filter_lists(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
-                         const Tensor& lists_) {
-  need(q_, "q", at::kBFloat16, 2);
-  need(p_, "p", at::kBFloat16, 2);
-  need(lists_, "lists", at::kInt, 3);
-  const c10::DeviceGuard g(q_.device());
-  const Tensor q = q_.contiguous(), p = p_.contiguous(), lists = lists_.contiguous();
-  TORCH_CHECK_VALUE(lists.size(1) == q.size(0), "lists must be [nlists, nq, r]");
-  Tensor packed = at::empty({q.size(0), k + 1}, q.options().dtype(at::kLong));
-  size_t wsb = 0;
-  Tensor ws = dist_ws(q, p.size(0), n_global, k, &wsb);
-  check_rc(drt_ip_topk_dist_filter_lists(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0),
-                                         n_global, (int32_t)q.size(1), (int32_t)k, id_offset,
-                                         (const uint32_t*)lists.data_ptr<int32_t>(), (int32_t)lists.size(0), nullptr,
-                                         (uint64_t*)packed.data_ptr<int64_t>(), ws.data_ptr(), wsb, stream_of(q)),
-           "drt_ip_topk_dist_filter_lists");
-  return packed;
-}
+  FilterPrelude(const Tensor& q_, const Tensor& p_, const Tensor& thr_, bool thr_is_lists, const Tensor& packed,
+                int64_t n_global_, int64_t k_, bool passes_ws = false)
+      : n_global(n_global_), k(k_) {
+    need(q_, "q", at::kBFloat16, 2);
+    need(p_, "p", at::kBFloat16, 2);
+    if (thr_is_lists) need(thr_, "lists", at::kInt, 3);
+    else need(thr_, "tau", at::kFloat, 1);
+    need(packed, "packed", at::kLong, 2);
+    guard.reset_device(q_.device());
+    q = q_.contiguous();
+    p = p_.contiguous();
+    thr = thr_is_lists ? thr_ : thr_.contiguous();
+    TORCH_CHECK_VALUE(thr_is_lists || thr.size(0) == q.size(0), "tau must hold one threshold per query");
+    TORCH_CHECK_VALUE(packed.is_contiguous() && packed.size(0) == q.size(0) && packed.size(1) == k + 1,
+                      "packed must be a contiguous [nq, k + 1] tensor");
+    ws = dist_ws(q, p.size(0), n_global, k, &wsb, passes_ws);
+  }
+  // fn(Q, nq, P (null for an empty shard), n_local, n_global, d, k, id_offset, mid..., ws, ws_bytes, stream)
+  template <class Fn, class... Mid>
+  void call(Fn fn, const char* what, int64_t id_offset, Mid... mid) const {
+    check_rc(fn(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0), n_global, (int32_t)q.size(1),
+                (int32_t)k, id_offset, mid..., ws.data_ptr(), wsb, stream_of(q)),
+             what);
+  }
+};
 
 // dist_filter writing into `packed` ([nq, k + 1] contiguous, e.g. a row slice of a group buffer); tau is
 // this batch's [nq] slice of a group's thresholds.
 void dist_filter_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
                       const Tensor& tau_, Tensor& packed) {
-  need(q_, "q", at::kBFloat16, 2);
-  need(p_, "p", at::kBFloat16, 2);
-  need(tau_, "tau", at::kFloat, 1);
-  need(packed, "packed", at::kLong, 2);
-  const c10::DeviceGuard g(q_.device());
-  const Tensor q = q_.contiguous(), p = p_.contiguous(), tau = tau_.contiguous();
-  TORCH_CHECK_VALUE(tau.size(0) == q.size(0), "tau must hold one threshold per query");
-  TORCH_CHECK_VALUE(packed.is_contiguous() && packed.size(0) == q.size(0) && packed.size(1) == k + 1,
-                    "packed must be a contiguous [nq, k + 1] tensor");
-  size_t wsb = 0;
-  Tensor ws = dist_ws(q, p.size(0), n_global, k, &wsb);
-  check_rc(drt_ip_topk_dist_filter(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0), n_global,
-                                   (int32_t)q.size(1), (int32_t)k, id_offset, tau.data_ptr<float>(),
-                                   (uint64_t*)packed.data_ptr<int64_t>(), ws.data_ptr(), wsb, stream_of(q)),
-           "drt_ip_topk_dist_filter");
+  const FilterPrelude f(q_, p_, tau_, false, packed, n_global, k);
+  f.call(drt_ip_topk_dist_filter, "drt_ip_topk_dist_filter", id_offset, f.thr.data_ptr<float>(),
+         (uint64_t*)packed.data_ptr<int64_t>());
+}
+
+Tensor dist_filter(const Tensor& q, const Tensor& p, int64_t n_global, int64_t k, int64_t id_offset,
+                   const Tensor& tau) {
+  need(q, "q", at::kBFloat16, 2);
+  Tensor packed = at::empty({q.size(0), k + 1}, q.options().dtype(at::kLong));
+  dist_filter_into(q, p, n_global, k, id_offset, tau, packed);
+  return packed;
 }
 
 // dist_filter over the shard in row chunks (chunk c = rows [starts[c], starts[c + 1])): one scan launch per
 // chunk, one hit list and one select -- the same packed lists as dist_filter_into over the whole shard.
 void dist_filter_chunks_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
                              const Tensor& tau_, at::IntArrayRef starts, Tensor& packed) {
-  need(q_, "q", at::kBFloat16, 2);
-  need(p_, "p", at::kBFloat16, 2);
-  need(tau_, "tau", at::kFloat, 1);
-  need(packed, "packed", at::kLong, 2);
-  const c10::DeviceGuard g(q_.device());
-  const Tensor q = q_.contiguous(), p = p_.contiguous(), tau = tau_.contiguous();
-  TORCH_CHECK_VALUE(tau.size(0) == q.size(0), "tau must hold one threshold per query");
-  TORCH_CHECK_VALUE(packed.is_contiguous() && packed.size(0) == q.size(0) && packed.size(1) == k + 1,
-                    "packed must be a contiguous [nq, k + 1] tensor");
-  TORCH_CHECK_VALUE(starts.size() >= 2 && starts.front() == 0 && starts.back() == p.size(0),
+  const FilterPrelude f(q_, p_, tau_, false, packed, n_global, k);
+  TORCH_CHECK_VALUE(starts.size() >= 2 && starts.front() == 0 && starts.back() == f.p.size(0),
                     "starts must run from 0 to the shard's row count");
   for (size_t c = 1; c < starts.size(); ++c) TORCH_CHECK_VALUE(starts[c - 1] <= starts[c], "starts must not decrease");
-  TORCH_CHECK_VALUE(q.size(1) <= 768, "chunked filtering takes d <= 768");
-  size_t wsb = 0;
-  Tensor ws = dist_ws(q, p.size(0), n_global, k, &wsb);
+  TORCH_CHECK_VALUE(f.q.size(1) <= 768, "chunked filtering takes d <= 768");
   const std::vector<int64_t> st(starts.begin(), starts.end());
-  check_rc(drt_ip_topk_dist_filter_chunks(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0),
-                                          n_global, (int32_t)q.size(1), (int32_t)k, id_offset,
-                                          tau.data_ptr<float>(), (uint64_t*)packed.data_ptr<int64_t>(), st.data(),
-                                          (int32_t)st.size() - 1, ws.data_ptr(), wsb, stream_of(q)),
-           "drt_ip_topk_dist_filter_chunks");
+  f.call(drt_ip_topk_dist_filter_chunks, "drt_ip_topk_dist_filter_chunks", id_offset, f.thr.data_ptr<float>(),
+         (uint64_t*)packed.data_ptr<int64_t>(), st.data(), (int32_t)st.size() - 1);
 }
 
 // dist_filter over a shard that is the whole corpus as `npasses` interleaved passes (pass p = the 16-row
@@ -457,65 +441,56 @@ void dist_filter_chunks_into(const Tensor& q_, const Tensor& p_, int64_t n_globa
 void filter_passes_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
                         const Tensor& tau_, int64_t npasses, int64_t r, Tensor& packed,
                         const c10::optional<Tensor>& tau1, const c10::optional<Tensor>& pass0) {
-  need(q_, "q", at::kBFloat16, 2);
-  need(p_, "p", at::kBFloat16, 2);
-  need(tau_, "tau", at::kFloat, 1);
-  need(packed, "packed", at::kLong, 2);
-  const c10::DeviceGuard g(q_.device());
-  const Tensor q = q_.contiguous(), p = p_.contiguous(), tau = tau_.contiguous();
-  TORCH_CHECK_VALUE(tau.size(0) == q.size(0), "tau must hold one threshold per query");
-  TORCH_CHECK_VALUE(packed.is_contiguous() && packed.size(0) == q.size(0) && packed.size(1) == k + 1,
-                    "packed must be a contiguous [nq, k + 1] tensor");
-  TORCH_CHECK_VALUE(q.size(1) <= 768, "interleaved filter passes take d <= 768");
+  const FilterPrelude f(q_, p_, tau_, false, packed, n_global, k, /*passes_ws=*/true);
+  TORCH_CHECK_VALUE(f.q.size(1) <= 768, "interleaved filter passes take d <= 768");
   TORCH_CHECK_VALUE(npasses >= 1 && npasses <= 1024, "npasses must be in [1, 1024]");
   if (tau1.has_value()) {
     need(*tau1, "tau1", at::kFloat, 1);
-    TORCH_CHECK_VALUE(tau1->is_contiguous() && tau1->size(0) == q.size(0), "tau1 must be a contiguous [nq] tensor");
+    TORCH_CHECK_VALUE(tau1->is_contiguous() && tau1->size(0) == f.q.size(0), "tau1 must be a contiguous [nq] tensor");
   }
   if (pass0.has_value()) {
     need(*pass0, "pass0", at::kInt, 2);
-    TORCH_CHECK_VALUE(pass0->is_contiguous() && pass0->size(0) == q.size(0) && pass0->size(1) == 4,
+    TORCH_CHECK_VALUE(pass0->is_contiguous() && pass0->size(0) == f.q.size(0) && pass0->size(1) == 4,
                       "pass0 must be a contiguous [nq, 4] tensor");
   }
-  const size_t wsb = drt_ip_topk_filter_passes_workspace(q.size(0), p.size(0), n_global, (int32_t)q.size(1), (int32_t)k);
-  TORCH_CHECK_VALUE(wsb > 0 || q.size(0) == 0, "unsupported dist shape nq=", q.size(0), " n_local=", p.size(0),
-                    " n_global=", n_global, " d=", q.size(1), " k=", k);
-  Tensor ws = workspace(q, wsb);
-  check_rc(drt_ip_topk_filter_passes(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0), n_global,
-                                     (int32_t)q.size(1), (int32_t)k, id_offset, tau.data_ptr<float>(),
-                                     (uint64_t*)packed.data_ptr<int64_t>(), (int32_t)npasses, (int32_t)r,
-                                     tau1.has_value() ? tau1->data_ptr<float>() : nullptr,
-                                     pass0.has_value() ? (uint32_t*)pass0->data_ptr<int32_t>() : nullptr,
-                                     ws.data_ptr(), wsb, stream_of(q)),
-           "drt_ip_topk_filter_passes");
+  f.call(drt_ip_topk_filter_passes, "drt_ip_topk_filter_passes", id_offset, f.thr.data_ptr<float>(),
+         (uint64_t*)packed.data_ptr<int64_t>(), (int32_t)npasses, (int32_t)r,
+         tau1.has_value() ? tau1->data_ptr<float>() : nullptr,
+         pass0.has_value() ? (uint32_t*)pass0->data_ptr<int32_t>() : nullptr);
+}
+
+// The fused threshold + filter for query rows [q0, q0 + nq) of lists [nlists, NQ, r]; `what` names the C
+// entry in the error text (the whole-set form keeps reporting drt_ip_topk_dist_filter_lists, which
+// forwards to the same drt_ip_topk_dist_filter_lists_at with q0 = 0 and NQ = nq).
+void filter_lists_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
+                       const Tensor& lists, int64_t q0, Tensor& packed, const char* what) {
+  const FilterPrelude f(q_, p_, lists, true, packed, n_global, k);
+  TORCH_CHECK_VALUE(lists.is_contiguous(), "lists must be a contiguous [nlists, NQ, r] tensor");
+  TORCH_CHECK_VALUE(q0 >= 0 && q0 + f.q.size(0) <= lists.size(1), "query rows [", q0, ", ", q0 + f.q.size(0),
+                    ") outside the lists' ", lists.size(1), " rows");
+  const int64_t r = lists.size(2);
+  TORCH_CHECK_VALUE(r == drt_ip_topk_sample_rank((int32_t)k), "lists hold ", r, " keys per query, k=", k, " needs ",
+                    drt_ip_topk_sample_rank((int32_t)k));
+  f.call(drt_ip_topk_dist_filter_lists_at, what, id_offset, (const uint32_t*)lists.data_ptr<int32_t>() + q0 * r,
+         (int32_t)lists.size(0), lists.size(1) * r, (float*)nullptr, (uint64_t*)packed.data_ptr<int64_t>());
 }
 
 // dist_filter_lists for query rows [q0, q0 + nq) of lists [nlists, NQ, r] gathered for a group of
 // batches, writing the packed lists into `packed` ([nq, k + 1], e.g. a row slice of a group buffer).
-void dist_filter_lists_into(const Tensor& q_, const Tensor& p_, int64_t n_global, int64_t k, int64_t id_offset,
+void dist_filter_lists_into(const Tensor& q, const Tensor& p, int64_t n_global, int64_t k, int64_t id_offset,
                             const Tensor& lists, int64_t q0, Tensor& packed) {
-  need(q_, "q", at::kBFloat16, 2);
-  need(p_, "p", at::kBFloat16, 2);
-  need(lists, "lists", at::kInt, 3);
-  need(packed, "packed", at::kLong, 2);
-  const c10::DeviceGuard g(q_.device());
-  const Tensor q = q_.contiguous(), p = p_.contiguous();
-  TORCH_CHECK_VALUE(lists.is_contiguous(), "lists must be a contiguous [nlists, NQ, r] tensor");
-  TORCH_CHECK_VALUE(q0 >= 0 && q0 + q.size(0) <= lists.size(1), "query rows [", q0, ", ", q0 + q.size(0),
-                    ") outside the lists' ", lists.size(1), " rows");
-  TORCH_CHECK_VALUE(packed.is_contiguous() && packed.size(0) == q.size(0) && packed.size(1) == k + 1,
-                    "packed must be a contiguous [nq, k + 1] tensor");
-  const int64_t r = lists.size(2);
-  TORCH_CHECK_VALUE(r == drt_ip_topk_sample_rank((int32_t)k), "lists hold ", r, " keys per query, k=", k, " needs ",
-                    drt_ip_topk_sample_rank((int32_t)k));
-  size_t wsb = 0;
-  Tensor ws = dist_ws(q, p.size(0), n_global, k, &wsb);
-  check_rc(drt_ip_topk_dist_filter_lists_at(q.data_ptr(), q.size(0), p.size(0) ? p.data_ptr() : nullptr, p.size(0),
-                                            n_global, (int32_t)q.size(1), (int32_t)k, id_offset,
-                                            (const uint32_t*)lists.data_ptr<int32_t>() + q0 * r,
-                                            (int32_t)lists.size(0), lists.size(1) * r, nullptr,
-                                            (uint64_t*)packed.data_ptr<int64_t>(), ws.data_ptr(), wsb, stream_of(q)),
-           "drt_ip_topk_dist_filter_lists_at");
+  filter_lists_into(q, p, n_global, k, id_offset, lists, q0, packed, "drt_ip_topk_dist_filter_lists_at");
+}
+
+Tensor dist_filter_lists(const Tensor& q, const Tensor& p, int64_t n_global, int64_t k, int64_t id_offset,
+                         const Tensor& lists_) {
+  need(q, "q", at::kBFloat16, 2);
+  need(p, "p", at::kBFloat16, 2);
+  need(lists_, "lists", at::kInt, 3);
+  TORCH_CHECK_VALUE(lists_.size(1) == q.size(0), "lists must be [nlists, nq, r]");
+  Tensor packed = at::empty({q.size(0), k + 1}, q.options().dtype(at::kLong));
+  filter_lists_into(q, p, n_global, k, id_offset, lists_.contiguous(), 0, packed, "drt_ip_topk_dist_filter_lists");
+  return packed;
 }
 
 std::tuple<Tensor, Tensor, Tensor> merge_packed(const Tensor& parts_, int64_t k, int64_t n_global, int64_t k_cert) {

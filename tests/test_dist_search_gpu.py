@@ -271,3 +271,37 @@ def test_top_r_sample_pass_lower_bounds_the_rth_sampled_key(dev, nq, n, d, data)
         wt = orc.desc_key_to_score(want[:, r - 1]).astype(np.float64)
         assert (gt <= wt + 1e-3).all()
         assert (np.abs(gt - wt) <= 1e-3).mean() >= 0.99
+
+
+@pytest.mark.parametrize("n,d,k,gmul,offmul", [
+    (5003, 64, 10, 8, 3),    # sampled threshold, ragged last tile
+    (3000, 832, 10, 8, 0),   # the wide-row kernel
+    (1500, 128, 10, 1, 0),   # below the cap: no sample, everything passes
+    (0, 128, 10, 0, 0),      # an empty shard of a 40000-row corpus
+])
+def test_dist_filter_lists_into_equals_dist_filter_on_query_slices(dev, n, d, k, gmul, offmul):
+    """kernels.dist_filter_lists_into (drt_ip_topk_dist_filter_lists_at: threshold from the query rows
+    [q0, q0 + nq) of lists gathered for a larger query set, then the filter) returns dist_filter's packed
+    lists for those rows bit for bit, and dist_filter_lists' on the sliced inputs -- for the whole set, a
+    slice of more than 128 queries across a 128-query boundary (the 32-queries-per-wave kernel) and a
+    short slice (the single-block kernel).  Integer data: exact scores."""
+    import torch
+    from denseretrievaltoolkits_amd import kernels
+    NQ = 300
+    rng = np.random.default_rng(n + d)
+    qt = to_dev_bf16(int_bf16(rng, (NQ, d), -4, 4), dev)
+    pt = (to_dev_bf16(int_bf16(rng, (n, d), -4, 4), dev) if n else
+          torch.empty((0, d), dtype=torch.bfloat16, device=dev))
+    n_global = gmul * n if n else 40000
+    off = offmul * n
+    lists = kernels.dist_sample(qt, pt, n_global, k).unsqueeze(0)
+    assert lists.shape == (1, NQ, kernels.sample_rank(k))
+    tau = kernels.dist_tau(lists, k)
+    want = kernels.dist_filter(qt, pt, n_global, k, off, tau)
+    for q0, nq in ((0, 300), (100, 200), (263, 37)):
+        buf = torch.full((nq, k + 1), -7, dtype=torch.int64, device=dev)
+        kernels.dist_filter_lists_into(qt[q0:q0 + nq], pt, n_global, k, off, lists, q0, buf)
+        sliced = kernels.dist_filter_lists(qt[q0:q0 + nq], pt, n_global, k, off, lists[:, q0:q0 + nq])
+        torch.cuda.synchronize()
+        assert torch.equal(buf, want[q0:q0 + nq]), (q0, nq)
+        assert torch.equal(buf, sliced), (q0, nq)
