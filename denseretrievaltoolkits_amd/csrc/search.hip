@@ -9,13 +9,13 @@
 //                    tau_q = the r-th largest sampled score (a lower bound of
 //                    the k-th score with probability 1 - 1e-9; certified in
 //                    step 4).  One shard: ip_scan16_kernel<DENSE> writes every
-//                    sampled score, kth_rank / kth_partial + kth_final pick the
-//                    r-th.  Distributed and grouped (drt_ip_topk_dist_sample):
+//                    sampled score, kth_rank / kth_partial + kth_final pick
+//                    the r-th.  Distributed and grouped (drt_ip_topk_dist_sample):
 //                    ip_scan16_kernel<TOPR> keeps each lane's best keys in
 //                    registers and kth_final takes the r-th of their union.
 //   2. filter pass   streams every shard row once from HBM through LDS
-//                    (global_load_lds into a ring of 16-row tiles, 5 slots at
-//                    d = 768), scores 16 rows x 16 queries per
+//                    (global_load_lds into a ring of 16-row tiles; at d = 768
+//                    5 slots, 6 in ip_scan32r), scores 16 rows x 16 queries per
 //                    v_mfma_f32_16x16x32_bf16 (queries resident in VGPRs for
 //                    the whole launch) and appends (score, row) keys >= tau_q
 //                    to a per-query list.  Kernels (launch_scan_d picks):
@@ -39,27 +39,22 @@
 //                    query's near-tie window by exact scores.
 // "Filter scan", "Canonical order", "One-GPU groups in row
 // chunks", "One-GPU groups as interleaved passes with a tightened threshold",
-// "Multi-GPU: global-threshold protocol".  The host side -- plans, the scan and
-// select launchers, the C entry points -- starts at "Host-side planning and
-// launch helpers"; the five filter entry points share the filter_* helpers
-// above drt_ip_topk_dist_filter.
+// "Multi-GPU: global-threshold protocol".  The select, kth_* and tighten kernels
+// of steps 1-3 live in select.hip and are reached through the launchers declared
+// in search_internal.h (device code is not relocatable: a kernel is launched only
+// from the unit that defines it).  The host side -- plans, the scan launcher, the
+// C entry points -- starts at "Host-side planning and launch helpers"; the five
+// filter entry points share the filter_* helpers above drt_ip_topk_dist_filter.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "drt_common.h"
 #include "profile.h"
+#include "search_internal.h"
 
 namespace drt {
 
-constexpr int kScanThreads = 256;  // 4 waves, one per SIMD
-constexpr int kQueriesPerWG = 128;  // 4 waves x 32 query columns
 constexpr int kHitCap = 1024;       // LDS hit list entries per work-group
-// Per-query hit counters sit one 128-B line apart (index q * kCntStride): every work-group's
-// flush increments the counters of all 128 queries of its block, and packed into 4 lines they
-// serialised in L2 (r02 A/B: see DESIGN.md §3).
-constexpr int kCntStride = 32;
-
 enum { SCAN_FILTER = 0, SCAN_DENSE = 1, SCAN_TOPR = 2 };
 // SCAN_TOPR (the grouped sample pass, round 6): instead of writing every sampled score, each lane keeps
 // the kTopRL best keys of its query over the rows it sees (its 4 rows of every tile of its work-group)
@@ -187,7 +182,7 @@ __device__ __forceinline__ void flush_hits_agg(const ScanArgs& a, int64_t qbase,
   }
 }
 
-template <int NT = kScanThreads>
+template <int NT>
 __device__ __forceinline__ void flush_hits(const ScanArgs& a, int64_t qbase, uint32_t n,
                                            const uint64_t* hk, const uint16_t* hq) {
   n = n < (uint32_t)kHitCap ? n : (uint32_t)kHitCap;
@@ -200,8 +195,7 @@ __device__ __forceinline__ void flush_hits(const ScanArgs& a, int64_t qbase, uin
 
 // ---------------------------------------------------------------------------
 // Production scan: 16-row tiles on v_mfma_f32_16x16x32_bf16, 5-slot LDS ring at d = 768
-// (up to 4 x 24 KiB in flight per CU while the waves compute, vs 2 x 48 KiB for the
-// 32-row ring above).
+// (4 x 24 KiB in flight per CU while the waves compute; ip_scan16r keeps all 5 slots in flight).
 //   B operand (queries, VGPR-resident): lane l holds Q[q0 + 16 b + (l&15)]
 //     [32 s + 8 (l>>4) .. +8] for column block b = 0, 1 and k-step s.
 //   A operand (corpus, LDS): lane l reads row (l&15), 16-B chunk 4 s + (l>>4).
@@ -211,14 +205,14 @@ __device__ __forceinline__ void flush_hits(const ScanArgs& a, int64_t qbase, uin
 // ---------------------------------------------------------------------------
 constexpr int kT16 = 16;
 
-template <int D, int NW = 4>
+template <int D, int NW>
 struct Scan16Cfg {
   static constexpr int KS = D / 32;                         // 16x16x32 k-steps
   static constexpr int TILE_BYTES = kT16 * D * 2;            // 24 KiB at d = 768
   static constexpr int GLDS_PER_TILE = TILE_BYTES / 1024;
   // every wave issues the same count (vmcnt bookkeeping); the remainder
   // instructions are duplicates of earlier ones (same bytes, same LDS address)
-  static constexpr int GLDS_PER_WAVE = (GLDS_PER_TILE + NW - 1) / NW;   // 6 (4 waves) / 3 (8 waves) at d = 768
+  static constexpr int GLDS_PER_WAVE = (GLDS_PER_TILE + NW - 1) / NW;   // 3 at d = 768 (8 waves)
   static constexpr int HITS_BYTES = kHitCap * 10 + 16 + 2 * kQueriesPerWG * 4;
   static constexpr int NBUF_RAW = (160 * 1024 - HITS_BYTES) / TILE_BYTES;
   // at d = 768 a 5-slot ring (4 tiles = 96 KiB in flight per CU) beat 6 slots in three alternating A/B
@@ -1022,999 +1016,6 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   if (my_tiles & 1) epilogue(a0, a1, rbA);
   else epilogue(b0, b1, rbB);
   if (wcnt) wave_flush_hits(a, qw, hk, hq, wcnt, lane);
-}
-
-// ---------------------------------------------------------------------------
-// Per-query selection.
-//
-// Fast path (every realistic input): one block per query,
-//   A  min/max of the scores,
-//   B  1024-bin histogram LINEAR IN THE SCORE VALUE (per-wave sub-histograms,
-//      so a dense score range does not serialise on a few LDS bins),
-//   C  suffix scan -> highest bin b with >= k elements at or above it,
-//   D  TOPK: gather every key in bins >= b into LDS (<= 4096 of them),
-//      bitonic sort on the 64-bit key (score desc, row asc), emit k;
-//      KTH:  tau = min score among bins >= b  (<= the k-th largest: safe).
-// Bin membership is one monotone float formula used by every pass, so the
-// selected set is always an upper set of the scores (ties stay together).
-// Fallback (degenerate data, e.g. >4096 equal scores): MSD radix select on
-// the full 64-bit key, 8 bits per pass, then the same sort.
-// ---------------------------------------------------------------------------
-enum { SEL_KEYS64 = 0, SEL_DENSE32 = 1 };
-enum { SEL_TOPK = 0, SEL_KTH = 1 };
-constexpr int kSelThreads = 512;
-constexpr int kSelWaves = kSelThreads / 64;
-constexpr int kSelMaxK = 2048;
-constexpr int kSelBins = 1024;
-constexpr int kSelBuf = 4096;
-constexpr int kSelKPT = 16;                          // keys per thread held in registers
-constexpr int kSelRegCap = kSelKPT * kSelThreads;    // 8192
-
-struct SelectArgs {
-  const void* in;
-  int64_t in_stride;        // elements per query row of `in`
-  const uint32_t* counts;   // KEYS64: [nq] hit counts; DENSE32: nullptr
-  int64_t n_in;             // DENSE32: valid entries per query
-  int64_t cap;              // KEYS64: capacity per query
-  int64_t n_total;          // rows the counts were taken over (certification)
-  int k;
-  int64_t nq;
-  // TOPK output
-  float* out_scores;
-  int64_t* out_ids;
-  int64_t ldo;
-  int64_t id_offset;
-  int32_t* status;          // may be null
-  const int32_t* qmap;      // optional: output row for block q (resolve path)
-  // KTH output
-  float* tau;
-  // distributed protocol: packed output [nq][k + 1] u64 = (desc score key << 32 | global id),
-  // entry k = flags (bit 0: overflow); with a global tau a short local list is not a failure
-  uint64_t* out_packed;
-  bool global_tau;
-  int k_cert;               // k of the certification (0: k); the refine stage selects kc >= k entries
-  // packed output of a filter whose later passes ran against a tightened threshold (tighten_kernel):
-  // [nq][4] u32 = the first pass's hit count c0, r_eff = its hits >= tau1, tightened (tau1 > tau0).  The
-  // list then holds every row >= tau1 plus first-pass rows in [tau0, tau1): it is the whole shard's list
-  // only if r_eff + (hits of the later passes) >= k -- otherwise flag bit 0 is set (not certified)
-  const uint32_t* pass0;
-};
-
-template <int INPUT>
-__device__ __forceinline__ uint64_t sel_load(const SelectArgs& a, int64_t q, int64_t j) {
-  if (INPUT == SEL_KEYS64) return ((const uint64_t*)a.in)[q * a.in_stride + j];
-  const uint32_t v = ((const uint32_t*)a.in)[q * a.in_stride + j];
-  return ((uint64_t)v << 32) | (uint64_t)(uint32_t)j;
-}
-
-__device__ __forceinline__ float key_score(uint64_t x) { return desc_key_to_score((uint32_t)(x >> 32)); }
-
-// bin kSelBins - 1 = best scores
-__device__ __forceinline__ int score_bin(float s, float smin, float scale) {
-  if (scale == 0.0f) return 0;
-  return hist_bin((s - smin) * scale, kSelBins, __builtin_signbit(s) ? 0 : kSelBins - 1);
-}
-
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, T* scratch, Op op) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[w] = v;
-  __syncthreads();
-  T r = scratch[0];
-#pragma unroll
-  for (int i = 1; i < kSelWaves; ++i) r = op(r, scratch[i]);
-  return r;
-}
-
-// Block-wide bitonic sort of buf[0..n) ascending (n a power of two, n <= 8 * NT).
-// The keys live in registers (element u * NT + tid in v[u]); a compare-exchange
-// at stride s runs in-thread (s >= NT), through LDS (64 <= s < NT: two
-// barriers) or as a cross-lane shuffle (s < 64, no barrier), so most of the
-// log2(n) * (log2(n) + 1) / 2 stages cost no block synchronisation.  Slots past
-// n hold the maximum key (they sort last and are never written back).
-template <typename T, int NT, int E, int US>
-__device__ __forceinline__ void sort_inthread(T (&v)[E], int size, int tid) {
-#pragma unroll
-  for (int u = 0; u < E; ++u) {
-    if ((u & US) == 0 && (u | US) < E) {
-      const int i = u * NT + tid;
-      const bool up = (i & size) == 0;
-      const T a = v[u], b = v[u | US];
-      v[u] = up ? (a < b ? a : b) : (a < b ? b : a);
-      v[u | US] = up ? (a < b ? b : a) : (a < b ? a : b);
-    }
-  }
-}
-
-template <typename T, int NT, int N>
-__device__ __forceinline__ void block_sort_fixed(T* buf, int n) {
-  constexpr int E = N / NT;
-  const int tid = threadIdx.x;
-  const T kMax = ~(T)0;
-  T v[E];
-#pragma unroll
-  for (int u = 0; u < E; ++u) {
-    const int i = u * NT + tid;
-    v[u] = i < n ? buf[i] : kMax;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int size = 2; size <= N; size <<= 1) {
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (stride >= NT) {
-        if (E >= 2 && stride == NT) sort_inthread<T, NT, E, 1>(v, size, tid);
-        else if (E >= 4 && stride == 2 * NT) sort_inthread<T, NT, E, 2>(v, size, tid);
-        else if (E >= 8) sort_inthread<T, NT, E, 4>(v, size, tid);
-      } else {
-        T p[E];
-        if (stride >= 64) {
-#pragma unroll
-          for (int u = 0; u < E; ++u) buf[u * NT + tid] = v[u];
-          __syncthreads();
-#pragma unroll
-          for (int u = 0; u < E; ++u) p[u] = buf[(u * NT + tid) ^ stride];
-          __syncthreads();
-        } else {
-#pragma unroll
-          for (int u = 0; u < E; ++u) p[u] = __shfl_xor(v[u], stride, 64);
-        }
-#pragma unroll
-        for (int u = 0; u < E; ++u) {
-          const int i = u * NT + tid;
-          const bool keep_min = ((i & stride) == 0) == ((i & size) == 0);
-          const T a = v[u], b = p[u];
-          v[u] = keep_min ? (a < b ? a : b) : (a < b ? b : a);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < E; ++u) {
-    const int i = u * NT + tid;
-    if (i < n) buf[i] = v[u];
-  }
-  __syncthreads();
-}
-
-template <typename T, int NT>
-__device__ __forceinline__ void block_sort(T* buf, int n) {
-  if (n <= 1) {
-    __syncthreads();
-    return;
-  }
-  if (n <= NT) block_sort_fixed<T, NT, NT>(buf, n);
-  else if (n <= 2 * NT) block_sort_fixed<T, NT, 2 * NT>(buf, n);
-  else if (n <= 4 * NT) block_sort_fixed<T, NT, 4 * NT>(buf, n);
-  else block_sort_fixed<T, NT, 8 * NT>(buf, n);
-}
-
-// Bitonic sort of buf[0..n2) ascending (n2 power of two, <= kSelBuf), whole block.
-__device__ __forceinline__ void block_bitonic(uint64_t* buf, int n2) { block_sort<uint64_t, kSelThreads>(buf, n2); }
-
-template <int INPUT, int OUTPUT>
-__global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
-  __shared__ uint32_t hist[kSelWaves][kSelBins];
-  __shared__ uint32_t suffix[kSelBins];
-  __shared__ float fscr[kSelWaves];
-  __shared__ uint64_t uscr[kSelWaves];
-  __shared__ uint64_t sh_prefix, sh_mask;
-  __shared__ int64_t sh_kk;
-  __shared__ int sh_done, sh_bin;
-  __shared__ uint32_t sh_nsel, sh_nside;
-  __shared__ __attribute__((aligned(16))) uint64_t buf[kSelBuf];
-
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int64_t q = blockIdx.x;
-  int64_t c_raw, c;
-  if (INPUT == SEL_KEYS64) {
-    c_raw = a.counts[q * kCntStride];
-    c = c_raw < a.cap ? c_raw : a.cap;
-  } else {
-    c_raw = a.n_in;
-    c = a.n_in;
-  }
-  const int64_t kk_total = (int64_t)a.k < c ? (int64_t)a.k : c;
-
-  if (OUTPUT == SEL_KTH && (c < (int64_t)a.k || c == 0)) {
-    if (tid == 0) a.tau[q] = -__builtin_inff();  // too few samples: keep everything
-    return;
-  }
-
-  bool fast_done = false;   // uniform
-  int nsel = 0;             // TOPK: entries in buf
-  if (c > (int64_t)a.k && c <= kSelRegCap) {
-    // every key loaded once (all loads in flight together), passes run on registers
-    uint64_t kr[kSelKPT];
-    float sc[kSelKPT];
-#pragma unroll
-    for (int u = 0; u < kSelKPT; ++u) {
-      const int64_t j = (int64_t)u * kSelThreads + tid;
-      const uint64_t x = sel_load<INPUT>(a, q, j < c ? j : 0);   // clamped: loads issue back to back
-      kr[u] = j < c ? x : ~0ull;
-    }
-    float lo = __builtin_inff(), hi = -__builtin_inff();
-#pragma unroll
-    for (int u = 0; u < kSelKPT; ++u) {
-      sc[u] = key_score(kr[u]);
-      if ((int64_t)u * kSelThreads + tid < c) {
-        lo = fminf(lo, sc[u]);
-        hi = fmaxf(hi, sc[u]);
-      }
-    }
-    lo = block_reduce(lo, fscr, [](float x, float y) { return fminf(x, y); });
-    hi = block_reduce(hi, fscr, [](float x, float y) { return fmaxf(x, y); });
-    const float range = hi - lo;
-    const float scale = hist_scale((float)kSelBins, range);
-    for (int i = tid; i < kSelWaves * kSelBins; i += kSelThreads) (&hist[0][0])[i] = 0;
-    __syncthreads();
-    int bn[kSelKPT];
-#pragma unroll
-    for (int u = 0; u < kSelKPT; ++u) {
-      bn[u] = -1;
-      if ((int64_t)u * kSelThreads + tid < c) {
-        bn[u] = score_bin(sc[u], lo, scale);
-        atomicAdd(&hist[wave][bn[u]], 1u);
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < kSelBins; i += kSelThreads) {
-      uint32_t t = 0;
-#pragma unroll
-      for (int w = 0; w < kSelWaves; ++w) t += hist[w][i];
-      suffix[i] = t;
-    }
-    __syncthreads();
-    for (int off = 1; off < kSelBins; off <<= 1) {
-      uint32_t v[kSelBins / kSelThreads];
-#pragma unroll
-      for (int u = 0; u < kSelBins / kSelThreads; ++u) {
-        const int i = tid + u * kSelThreads;
-        v[u] = suffix[i] + (i + off < kSelBins ? suffix[i + off] : 0u);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < kSelBins / kSelThreads; ++u) suffix[tid + u * kSelThreads] = v[u];
-      __syncthreads();
-    }
-    if (tid == 0) sh_bin = 0;
-    __syncthreads();
-    for (int i = tid; i < kSelBins; i += kSelThreads) {
-      const bool ok = (int64_t)suffix[i] >= kk_total;
-      const bool next_ok = (i + 1 < kSelBins) && (int64_t)suffix[i + 1] >= kk_total;
-      if (ok && !next_ok) sh_bin = i;
-    }
-    __syncthreads();
-    const int b = sh_bin;
-    if (OUTPUT == SEL_KTH) {
-      float t = __builtin_inff();
-#pragma unroll
-      for (int u = 0; u < kSelKPT; ++u)
-        if (bn[u] >= b) t = fminf(t, sc[u]);
-      t = block_reduce(t, fscr, [](float x, float y) { return fminf(x, y); });
-      if (tid == 0) a.tau[q] = t;
-      return;
-    }
-    const uint32_t cnt_sel = suffix[b];
-    const uint32_t c_above = (b + 1 < kSelBins) ? suffix[b + 1] : 0u;
-    const uint32_t cnt_b = cnt_sel - c_above;
-    if (cnt_b <= (uint32_t)(kSelBuf / 2) && kk_total <= kSelBuf / 2) {
-      uint64_t* side = buf + kSelBuf / 2;
-      if (tid == 0) {
-        sh_nsel = 0;
-        sh_nside = 0;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < kSelKPT; ++u) {
-        if (bn[u] > b) buf[atomicAdd(&sh_nsel, 1u)] = kr[u];
-        else if (bn[u] == b) side[atomicAdd(&sh_nside, 1u)] = kr[u];
-      }
-      __syncthreads();
-      const int ns = (int)sh_nside;
-      int m2 = 1;
-      while (m2 < ns) m2 <<= 1;
-      for (int i = ns + tid; i < m2; i += kSelThreads) side[i] = ~0ull;
-      __syncthreads();
-      block_bitonic(side, m2);
-      const int need = (int)kk_total - (int)c_above;
-      for (int i = tid; i < need; i += kSelThreads) buf[c_above + i] = side[i];
-      __syncthreads();
-      nsel = (int)kk_total;
-      fast_done = true;
-    } else if (cnt_sel <= (uint32_t)kSelBuf) {
-      if (tid == 0) sh_nsel = 0;
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < kSelKPT; ++u)
-        if (bn[u] >= b) buf[atomicAdd(&sh_nsel, 1u)] = kr[u];
-      __syncthreads();
-      nsel = (int)sh_nsel;
-      fast_done = true;
-    }
-  } else if (c > (int64_t)a.k) {
-    // ---- A: score range
-    float lo = __builtin_inff(), hi = -__builtin_inff();
-    for (int64_t j = tid; j < c; j += kSelThreads) {
-      const float s = key_score(sel_load<INPUT>(a, q, j));
-      lo = fminf(lo, s);
-      hi = fmaxf(hi, s);
-    }
-    lo = block_reduce(lo, fscr, [](float x, float y) { return fminf(x, y); });
-    hi = block_reduce(hi, fscr, [](float x, float y) { return fmaxf(x, y); });
-    const float range = hi - lo;
-    const float scale = hist_scale((float)kSelBins, range);
-    // ---- B: per-wave histograms
-    for (int i = tid; i < kSelWaves * kSelBins; i += kSelThreads) (&hist[0][0])[i] = 0;
-    __syncthreads();
-    for (int64_t j = tid; j < c; j += kSelThreads) {
-      const float s = key_score(sel_load<INPUT>(a, q, j));
-      atomicAdd(&hist[wave][score_bin(s, lo, scale)], 1u);
-    }
-    __syncthreads();
-    for (int i = tid; i < kSelBins; i += kSelThreads) {
-      uint32_t t = 0;
-#pragma unroll
-      for (int w = 0; w < kSelWaves; ++w) t += hist[w][i];
-      suffix[i] = t;
-    }
-    __syncthreads();
-    // ---- C: inclusive suffix sum (Hillis-Steele over 1024 bins)
-    for (int off = 1; off < kSelBins; off <<= 1) {
-      uint32_t v[kSelBins / kSelThreads];
-#pragma unroll
-      for (int u = 0; u < kSelBins / kSelThreads; ++u) {
-        const int i = tid + u * kSelThreads;
-        v[u] = suffix[i] + (i + off < kSelBins ? suffix[i + off] : 0u);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < kSelBins / kSelThreads; ++u) suffix[tid + u * kSelThreads] = v[u];
-      __syncthreads();
-    }
-    // highest bin b with suffix[b] >= kk_total (suffix is non-increasing in b)
-    if (tid == 0) sh_bin = 0;
-    __syncthreads();
-    for (int i = tid; i < kSelBins; i += kSelThreads) {
-      const bool ok = (int64_t)suffix[i] >= kk_total;
-      const bool next_ok = (i + 1 < kSelBins) && (int64_t)suffix[i + 1] >= kk_total;
-      if (ok && !next_ok) sh_bin = i;
-    }
-    __syncthreads();
-    const int b = sh_bin;
-    const uint32_t cnt_sel = suffix[b];
-    if (OUTPUT == SEL_KTH) {
-      // ---- D(KTH): tau = min score in bins >= b  (a lower bound of the k-th largest)
-      float t = __builtin_inff();
-      for (int64_t j = tid; j < c; j += kSelThreads) {
-        const float s = key_score(sel_load<INPUT>(a, q, j));
-        if (score_bin(s, lo, scale) >= b) t = fminf(t, s);
-      }
-      t = block_reduce(t, fscr, [](float x, float y) { return fminf(x, y); });
-      if (tid == 0) a.tau[q] = t;
-      return;
-    }
-    const uint32_t c_above = (b + 1 < kSelBins) ? suffix[b + 1] : 0u;   // bins above b: all selected
-    const uint32_t cnt_b = cnt_sel - c_above;                             // boundary bin
-    if (cnt_b <= (uint32_t)(kSelBuf / 2) && kk_total <= kSelBuf / 2) {
-      // ---- D(TOPK): bins > b straight into buf[0, c_above); the boundary bin
-      // into buf[kSelBuf/2, ...), sorted alone, its best (kk - c_above) appended:
-      // exactly kk keys reach the final sort.
-      uint64_t* side = buf + kSelBuf / 2;
-      if (tid == 0) {
-        sh_nsel = 0;
-        sh_nside = 0;
-      }
-      __syncthreads();
-      for (int64_t j = tid; j < c; j += kSelThreads) {
-        const uint64_t x = sel_load<INPUT>(a, q, j);
-        const int bx = score_bin(key_score(x), lo, scale);
-        if (bx > b) buf[atomicAdd(&sh_nsel, 1u)] = x;
-        else if (bx == b) side[atomicAdd(&sh_nside, 1u)] = x;
-      }
-      __syncthreads();
-      const int ns = (int)sh_nside;
-      int m2 = 1;
-      while (m2 < ns) m2 <<= 1;
-      for (int i = ns + tid; i < m2; i += kSelThreads) side[i] = ~0ull;
-      __syncthreads();
-      block_bitonic(side, m2);
-      const int need = (int)kk_total - (int)c_above;
-      for (int i = tid; i < need; i += kSelThreads) buf[c_above + i] = side[i];
-      __syncthreads();
-      nsel = (int)kk_total;
-      fast_done = true;
-    } else if (cnt_sel <= (uint32_t)kSelBuf) {
-      // ---- D(TOPK): gather the whole upper set, sort, emit
-      if (tid == 0) sh_nsel = 0;
-      __syncthreads();
-      for (int64_t j = tid; j < c; j += kSelThreads) {
-        const uint64_t x = sel_load<INPUT>(a, q, j);
-        if (score_bin(key_score(x), lo, scale) >= b) {
-          const uint32_t p = atomicAdd(&sh_nsel, 1u);
-          if (p < (uint32_t)kSelBuf) buf[p] = x;
-        }
-      }
-      __syncthreads();
-      nsel = (int)sh_nsel;
-      fast_done = true;
-    }
-  }
-
-  if (!fast_done) {
-    // ---- fallback / small input: MSD radix select on 64-bit keys
-    if (tid == 0) {
-      sh_prefix = 0;
-      sh_mask = 0;
-      sh_kk = kk_total;
-      sh_done = (c <= (int64_t)a.k) ? 1 : 0;  // everything selected
-      if (c <= (int64_t)a.k) {
-        sh_prefix = ~0ull;
-        sh_mask = ~0ull;
-      }
-    }
-    __syncthreads();
-    uint32_t* h0 = &hist[0][0];
-    for (int shift = 56; shift >= 0 && !sh_done; shift -= 8) {
-      for (int i = tid; i < 256; i += kSelThreads) h0[i] = 0;
-      __syncthreads();
-      const uint64_t prefix = sh_prefix, mask = sh_mask;
-      for (int64_t j = tid; j < c; j += kSelThreads) {
-        const uint64_t x = sel_load<INPUT>(a, q, j);
-        if ((x & mask) == prefix) atomicAdd(&h0[(x >> shift) & 255], 1u);
-      }
-      __syncthreads();
-      if (tid < 64) {
-        const uint32_t b0 = h0[4 * tid], b1 = h0[4 * tid + 1], b2 = h0[4 * tid + 2], b3 = h0[4 * tid + 3];
-        const uint32_t s4 = b0 + b1 + b2 + b3;
-        uint32_t incl = s4;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t v = __shfl_up(incl, o, 64);
-          if (tid >= o) incl += v;
-        }
-        const uint32_t excl = incl - s4;
-        const int64_t kk = sh_kk;
-        if ((int64_t)excl < kk && kk <= (int64_t)incl) {
-          uint32_t run = excl;
-          const uint32_t bb[4] = {b0, b1, b2, b3};
-          int d = 0;
-          uint32_t cnt = 0;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if ((int64_t)(run + bb[t]) >= kk) {
-              d = 4 * tid + t;
-              cnt = bb[t];
-              break;
-            }
-            run += bb[t];
-          }
-          const int64_t rem = kk - run;
-          sh_prefix = prefix | ((uint64_t)d << shift);
-          sh_mask = mask | (255ull << shift);
-          sh_kk = rem;
-          if ((int64_t)cnt == rem) sh_done = 1;  // whole bucket selected
-        }
-      }
-      __syncthreads();
-    }
-    const uint64_t thr = sh_prefix | ~sh_mask;  // every key whose masked value <= prefix
-    if (tid == 0) sh_nsel = 0;
-    __syncthreads();
-    for (int64_t j = tid; j < c; j += kSelThreads) {
-      const uint64_t x = sel_load<INPUT>(a, q, j);
-      if (x <= thr) {
-        const uint32_t p = atomicAdd(&sh_nsel, 1u);
-        if (p < (uint32_t)kSelBuf) buf[p] = x;
-      }
-    }
-    __syncthreads();
-    nsel = (int)sh_nsel;
-  }
-
-  nsel = nsel < kSelBuf ? nsel : kSelBuf;
-  int n2 = 1;
-  while (n2 < nsel) n2 <<= 1;
-  for (int i = nsel + tid; i < n2; i += kSelThreads) buf[i] = ~0ull;
-  __syncthreads();
-  block_bitonic(buf, n2);
-
-  const int64_t orow = a.qmap ? (int64_t)a.qmap[q] : q;
-  if (a.out_packed) {
-    uint64_t* op = a.out_packed + orow * (int64_t)(a.k + 1);
-    for (int j = tid; j < a.k; j += kSelThreads) {
-      if (j < kk_total) {
-        const uint64_t x = buf[j];
-        op[j] = (x & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)(a.id_offset + (int64_t)(x & 0xFFFFFFFFull));
-      } else {
-        op[j] = ~0ull;
-      }
-    }
-    if (tid == 0) {
-      const uint64_t nval = (uint64_t)(kk_total < a.k ? kk_total : a.k);
-      // bit 0: overflow (more hits than the list buffer held); bit 1: truncated (more hits than the k
-      // entries written -- what a merge of capped exchange lists certifies against, round 6)
-      bool bad = INPUT == SEL_KEYS64 && c_raw > a.cap;
-      if (INPUT == SEL_KEYS64 && a.pass0) {
-        const uint32_t* t = a.pass0 + q * 4;
-        if (t[2] && (int64_t)t[1] + (c_raw - (int64_t)t[0]) < (int64_t)a.k) bad = true;
-      }
-      op[a.k] = (nval << 32) | (bad ? 1ull : 0ull) | (c_raw > (int64_t)a.k ? 2ull : 0ull);
-    }
-    return;
-  }
-  float* os = a.out_scores + orow * a.ldo;
-  int64_t* oi = a.out_ids + orow * a.ldo;
-  for (int j = tid; j < a.k; j += kSelThreads) {
-    if (j < kk_total) {
-      const uint64_t x = buf[j];
-      os[j] = key_score(x);
-      oi[j] = a.id_offset + (int64_t)(x & 0xFFFFFFFFull);
-    } else {
-      os[j] = kPadScore;
-      oi[j] = -1;
-    }
-  }
-  if (a.status && tid == 0) {
-    int st = 0;
-    if (INPUT == SEL_KEYS64) {
-      if (c_raw > a.cap) st = 1;                                                       // overflow
-      const int64_t kq = a.k_cert > 0 ? a.k_cert : a.k;
-      if (!a.global_tau && c_raw < kq && c_raw < a.n_total) st = 1;                    // threshold too high
-    }
-    a.status[orow] = st;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Tightened threshold after the first of a shard's interleaved filter passes
-// (drt_ip_topk_filter_passes): tau1[q] = the score of the r-th best key the first pass
-// collected (exactly: MSD radix select on the 32-bit score key, 8 bits per step) when it
-// collected c0 >= r of them, else tau0[q] (also for an inactive query, tau0 = NaN, and for a
-// list that overflowed `cap`).  pass0[q] = {c0, r_eff = first-pass keys scoring >= tau1 (ties
-// count), tau1 > tau0, 0}: what the final select certifies the list with (SelectArgs::pass0).
-// One block per query; the list (~cap / 4 / passes keys) is read from L2 five times.
-// ---------------------------------------------------------------------------
-constexpr int kTightThreads = 256;
-
-__global__ __launch_bounds__(kTightThreads) void tighten_kernel(const uint64_t* keys, int64_t cap,
-                                                                const uint32_t* counts, const float* tau0, int r,
-                                                                float* tau1, uint32_t* pass0) {
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t sh_prefix, sh_rem;
-  __shared__ uint32_t red[kTightThreads / 64];
-  const int tid = threadIdx.x;
-  const int64_t q = blockIdx.x;
-  const uint32_t c = counts[q * kCntStride];
-  const float t0 = tau0[q];
-  if (!((int64_t)c <= cap && c >= (uint32_t)r && t0 == t0)) {
-    if (tid == 0) {
-      tau1[q] = t0;
-      pass0[q * 4 + 0] = c;
-      pass0[q * 4 + 1] = c;
-      pass0[q * 4 + 2] = 0;
-      pass0[q * 4 + 3] = 0;
-    }
-    return;
-  }
-  const uint64_t* kq = keys + q * cap;
-  uint32_t prefix = 0, mask = 0, rem = (uint32_t)r;   // the rem-th smallest key among those matching prefix
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    hist[tid] = 0;
-    __syncthreads();
-    for (uint32_t j = tid; j < c; j += kTightThreads) {
-      const uint32_t key = (uint32_t)(kq[j] >> 32);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {
-      const uint32_t bb[4] = {hist[4 * tid], hist[4 * tid + 1], hist[4 * tid + 2], hist[4 * tid + 3]};
-      const uint32_t s4 = bb[0] + bb[1] + bb[2] + bb[3];
-      uint32_t incl = s4;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += v;
-      }
-      uint32_t run = incl - s4;
-      if (run < rem && rem <= incl) {   // exactly one lane: at least rem keys match the prefix
-        int dgt = 4 * tid;
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          if (dgt == 4 * tid + t && run + bb[t] < rem) {
-            run += bb[t];
-            ++dgt;
-          }
-        }
-        sh_prefix = prefix | ((uint32_t)dgt << shift);
-        sh_rem = rem - run;
-      }
-    }
-    __syncthreads();
-    prefix = sh_prefix;
-    rem = sh_rem;
-    mask |= 255u << shift;
-  }
-  const float t1 = desc_key_to_score(prefix);
-  uint32_t n = 0;
-  for (uint32_t j = tid; j < c; j += kTightThreads) n += key_score(kq[j]) >= t1 ? 1u : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = n;
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t tot = 0;
-    for (int w = 0; w < kTightThreads / 64; ++w) tot += red[w];
-    tau1[q] = t1;
-    pass0[q * 4 + 0] = c;
-    pass0[q * 4 + 1] = tot;
-    pass0[q * 4 + 2] = t1 > t0 ? 1u : 0u;
-    pass0[q * 4 + 3] = 0;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Sample threshold: tau_q = score of the r-th best sampled key.
-// kth_partial: grid (chunks, nq); each block LDS-sorts one 4096-key chunk of
-//              the dense sample row and keeps its best r keys.
-// kth_final:   grid nq; sorts the chunks' survivors (<= 4096), picks the r-th.
-// Padding keys are 0xFFFFFFFF (sort last, never chosen ahead of real keys).
-// ---------------------------------------------------------------------------
-constexpr int kKthChunk = 4096;
-constexpr int kKthThreads = 512;
-
-__device__ __forceinline__ void block_bitonic_u32(uint32_t* buf, int n2) { block_sort<uint32_t, kKthThreads>(buf, n2); }
-
-// Best r keys of one 4096-key chunk.  Keys live in registers (8 per thread);
-// a 256-bin histogram linear in the score value (per-wave sub-histograms)
-// finds the bin holding rank r, only the keys in the bins up to it (~r + a
-// few) are gathered and sorted.  Degenerate chunks (> 1024 keys tied around
-// rank r) fall back to sorting the whole chunk.
-constexpr int kKthPer = kKthChunk / kKthThreads;   // 8 keys per thread
-constexpr int kKthBins = 256;
-constexpr int kKthSel = 1024;
-
-__global__ __launch_bounds__(kKthThreads) void kth_partial_kernel(const uint32_t* in, int64_t stride, int64_t n,
-                                                                  int r, uint32_t* part) {
-  __shared__ __attribute__((aligned(16))) uint32_t buf[kKthChunk];
-  __shared__ uint32_t hist[kKthThreads / 64][kKthBins];
-  __shared__ float red[2][kKthThreads / 64];
-  __shared__ uint32_t sh_n;
-  __shared__ int sh_bin;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t q = blockIdx.y;
-  const int nchunk = gridDim.x;
-  const int64_t j0 = (int64_t)blockIdx.x * kKthChunk;
-  const int cnt = (int)(n - j0 < kKthChunk ? n - j0 : kKthChunk);
-  const uint32_t* src = in + q * stride + j0;
-
-  uint32_t key[kKthPer];
-  // thread t holds keys 4t..4t+3 and 2048+4t..2048+4t+3 (two coalesced 16-B loads)
-#pragma unroll
-  for (int v = 0; v < 2; ++v) {
-    const int base = v * (kKthChunk / 2) + 4 * tid;
-    if (base + 3 < cnt) {
-      const u32x4 x = *(const u32x4*)(src + base);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) key[4 * v + u] = x[u];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) key[4 * v + u] = base + u < cnt ? src[base + u] : 0xFFFFFFFFu;
-    }
-  }
-  // score range over real keys
-  float hi = -__builtin_inff(), lo = __builtin_inff();
-#pragma unroll
-  for (int e = 0; e < kKthPer; ++e) {
-    if (key[e] != 0xFFFFFFFFu) {
-      const float sc = desc_key_to_score(key[e]);
-      hi = fmaxf(hi, sc);
-      lo = fminf(lo, sc);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-    lo = fminf(lo, __shfl_xor(lo, o, 64));
-  }
-  if (lane == 0) {
-    red[0][wave] = hi;
-    red[1][wave] = lo;
-  }
-  for (int i = tid; i < (kKthThreads / 64) * kKthBins; i += kKthThreads) (&hist[0][0])[i] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < kKthThreads / 64; ++w) {
-    hi = fmaxf(hi, red[0][w]);
-    lo = fminf(lo, red[1][w]);
-  }
-  const float range = hi - lo;
-  const float scale = hist_scale((float)kKthBins, range);
-  // bin 0 = best scores
-  int bins[kKthPer];
-#pragma unroll
-  for (int e = 0; e < kKthPer; ++e) {
-    int bb = kKthBins;  // padding
-    if (key[e] != 0xFFFFFFFFu) {
-      const float sc = desc_key_to_score(key[e]);
-      bb = scale == 0.0f ? 0 : hist_bin((hi - sc) * scale, kKthBins, __builtin_signbit(sc) ? kKthBins - 1 : 0);
-      atomicAdd(&hist[wave][bb], 1u);
-    }
-    bins[e] = bb;
-  }
-  __syncthreads();
-  if (tid < 64) {
-    uint32_t c4[4];
-    uint32_t s4 = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int w = 0; w < kKthThreads / 64; ++w) v += hist[w][4 * tid + t];
-      c4[t] = v;
-      s4 += v;
-    }
-    uint32_t incl = s4;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = __shfl_up(incl, o, 64);
-      if (tid >= o) incl += v;
-    }
-    uint32_t run = incl - s4;
-    if (tid == 63 && incl < (uint32_t)r) sh_bin = kKthBins - 1;  // fewer than r real keys: take all
-    if (run < (uint32_t)r && (uint32_t)r <= incl) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (run + c4[t] >= (uint32_t)r) {
-          sh_bin = 4 * tid + t;
-          break;
-        }
-        run += c4[t];
-      }
-    }
-  }
-  if (tid == 0) sh_n = 0;
-  __syncthreads();
-  const int b = sh_bin;
-  // gather keys of bins <= b
-#pragma unroll
-  for (int e = 0; e < kKthPer; ++e) {
-    if (bins[e] <= b) {
-      const uint32_t pos = atomicAdd(&sh_n, 1u);
-      if (pos < (uint32_t)kKthSel) buf[pos] = key[e];
-    }
-  }
-  __syncthreads();
-  int nsel = (int)sh_n;
-  if (nsel > kKthSel) {
-    // degenerate: sort the whole chunk
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) buf[v * (kKthChunk / 2) + 4 * tid + u] = key[4 * v + u];
-    nsel = kKthChunk;
-  }
-  int n2 = 1;
-  while (n2 < nsel) n2 <<= 1;
-  for (int i = nsel + tid; i < n2; i += kKthThreads) buf[i] = 0xFFFFFFFFu;
-  __syncthreads();
-  block_bitonic_u32(buf, n2);
-  uint32_t* o = part + (q * nchunk + blockIdx.x) * r;
-  for (int i = tid; i < r; i += kKthThreads) o[i] = i < nsel ? buf[i] : 0xFFFFFFFFu;
-}
-
-// Element i of list l for query q lives at part[l * lstride + q * qstride + i], i < r.
-// Writes tau[q] (r-th best score; -inf if fewer than r real keys) and/or the
-// sorted best r keys best[q * r + i]; zero (optional): zero[q] = 0 (the filter's hit
-// counters, so the fused distributed filter needs no separate memset launch).
-__global__ __launch_bounds__(kKthThreads) void kth_final_kernel(const uint32_t* part, int nlists, int r,
-                                                                int64_t lstride, int64_t qstride, float* tau,
-                                                                uint32_t* best, uint32_t* zero, int len) {
-  __shared__ uint32_t buf[kKthChunk];
-  const int64_t q = blockIdx.x;
-  if (zero && threadIdx.x == 0) zero[q * kCntStride] = 0;
-  const int tot = nlists * len;   // nlists lists of len keys each (len = r: best-r lists)
-  {
-    uint32_t tmp[kKthChunk / kKthThreads];
-#pragma unroll
-    for (int u = 0; u < kKthChunk / kKthThreads; ++u) {
-      const int i = threadIdx.x + u * kKthThreads;
-      const int ic = i < tot ? i : 0;
-      const uint32_t x = part[(int64_t)(ic / len) * lstride + q * qstride + (ic % len)];
-      tmp[u] = i < tot ? x : 0xFFFFFFFFu;
-    }
-#pragma unroll
-    for (int u = 0; u < kKthChunk / kKthThreads; ++u) buf[threadIdx.x + u * kKthThreads] = tmp[u];
-  }
-  __syncthreads();
-  int n2 = 1;
-  while (n2 < tot) n2 <<= 1;
-  block_bitonic_u32(buf, n2);
-  if (tau && threadIdx.x == 0) {
-    const uint32_t kr = buf[r - 1];
-    tau[q] = (kr == 0xFFFFFFFFu) ? -__builtin_inff() : desc_key_to_score(kr);
-  }
-  if (best)
-    for (int i = threadIdx.x; i < r; i += kKthThreads) best[q * r + i] = buf[i];
-}
-
-// Sample threshold in ONE launch (one-GPU search, samples up to kRankThreads * kRankPer keys --
-// 70,801 at 10M rows and k = 1000): one 1024-thread work-group per query holds the whole sample
-// row in registers; round 4: the r-th best of the 1024 per-thread best keys bounds the answer, so only
-// those 1024 keys go through the 1024-bin histogram (not every sampled key: 70k LDS atomics per query,
-// mostly on the crowded middle bins), the keys no worse than that bound (~r of them) are sorted in
-// LDS and tau = the r-th best -- the same key kth_partial + kth_final pick (both exact), without the
-// chunk pass, its survivor lists and the second launch.  More than kRankBuf candidates (ties / a
-// degenerate score range) fall back to an exact MSD radix select over the candidates.  Also zeroes
-// the hit counter.
-constexpr int kRankThreads = 1024;
-constexpr int kRankPerMax = 80;   // keys per thread (register-resident); smaller samples take 8 / 24
-constexpr int kRankBins = 1024;
-constexpr int kRankBuf = 2048;
-constexpr int64_t kRankMaxKeys = (int64_t)kRankThreads * kRankPerMax;
-
-template <int kRankPer>
-__global__ __launch_bounds__(kRankThreads) void kth_rank_kernel(const uint32_t* in, int64_t stride, int64_t n, int r,
-                                                                float* tau, uint32_t* zero) {
-  __shared__ uint32_t hist[kRankBins];
-  __shared__ __attribute__((aligned(16))) uint32_t buf[kRankBuf];
-  __shared__ float red[2][kRankThreads / 64];
-  __shared__ uint32_t wsum[kRankThreads / 64];
-  __shared__ uint32_t sh_n, sh_rem, sh_prefix;
-  __shared__ int sh_bin;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t q = blockIdx.x;
-  if (zero && tid == 0) zero[q * kCntStride] = 0;
-  const uint32_t* src = in + q * stride;
-  constexpr uint32_t kPad = 0xFFFFFFFFu;
-  // thread t holds keys j * 4096 + 4t + [0, 4), j < kRankPer / 4 (coalesced 16-B loads; stride % 4 == 0)
-  uint32_t key[kRankPer];
-#pragma unroll
-  for (int j = 0; j < kRankPer / 4; ++j) {
-    const int64_t base = (int64_t)j * (4 * kRankThreads) + 4 * tid;
-    if (base + 3 < n) {
-      const u32x4 x = *(const u32x4*)(src + base);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) key[4 * j + u] = x[u];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) key[4 * j + u] = base + u < n ? src[base + u] : kPad;
-    }
-  }
-  // Candidates without a histogram of every key: the r best of the 1024 per-thread best keys are r
-  // distinct keys, so the r-th best key overall is no worse than the r-th best thread-best, K_r.
-  // A 1024-bin histogram of the thread-bests (1024 LDS atomics instead of one per sampled key)
-  // brackets K_r by bin b; T = the worst thread-best in bins <= b (>= K_r); every key <= T is a
-  // candidate -- the r best keys are among them, typically with few others (the thread-bests of
-  // those bins plus the rare second top key of one thread).
-  uint32_t best = kPad;
-#pragma unroll
-  for (int e = 0; e < kRankPer; ++e) best = key[e] < best ? key[e] : best;   // kPad = the largest key
-  float hi = -__builtin_inff(), lo = __builtin_inff();
-  if (best != kPad) {
-    const float sc = desc_key_to_score(best);
-    hi = sc;
-    lo = sc;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-    lo = fminf(lo, __shfl_xor(lo, o, 64));
-  }
-  if (lane == 0) {
-    red[0][wave] = hi;
-    red[1][wave] = lo;
-  }
-  hist[tid] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < kRankThreads / 64; ++w) {
-    hi = fmaxf(hi, red[0][w]);
-    lo = fminf(lo, red[1][w]);
-  }
-  const float range = hi - lo;
-  const float scale = hist_scale((float)kRankBins, range);
-  // bin 0 = best scores; monotone in the key
-  auto bin_of = [&](uint32_t kk) {
-    if (scale == 0.0f) return 0;
-    const float sc = desc_key_to_score(kk);
-    return hist_bin((hi - sc) * scale, kRankBins, __builtin_signbit(sc) ? kRankBins - 1 : 0);
-  };
-  if (best != kPad) atomicAdd(&hist[bin_of(best)], 1u);
-  __syncthreads();
-  {
-    const uint32_t v = hist[tid];
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    if (tid == 0) {
-      sh_n = 0;
-      sh_prefix = 0;   // T below (max over the selected thread-bests)
-    }
-    __syncthreads();
-    uint32_t off = 0;
-    for (int w = 0; w < wave; ++w) off += wsum[w];
-    incl += off;
-    const uint32_t excl = incl - v;
-    if (excl < (uint32_t)r && (uint32_t)r <= incl) sh_bin = tid;
-    // fewer than r thread-bests: every real key is a candidate
-    if (tid == kRankThreads - 1 && incl < (uint32_t)r) sh_bin = -1;
-  }
-  __syncthreads();
-  const int b = sh_bin;
-  if (b >= 0) {
-    // T = the worst (largest) thread-best key in bins <= b
-    uint32_t t = (best != kPad && bin_of(best) <= b) ? best : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint32_t u = __shfl_xor(t, o, 64);
-      t = u > t ? u : t;
-    }
-    if (lane == 0) atomicMax(&sh_prefix, t);
-  }
-  __syncthreads();
-  const uint32_t T = b >= 0 ? sh_prefix : kPad - 1u;
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < kRankPer; ++e) {
-    if (key[e] <= T) {
-      const uint32_t pos = atomicAdd(&sh_n, 1u);
-      if (pos < (uint32_t)kRankBuf) buf[pos] = key[e];
-    }
-  }
-  __syncthreads();
-  const int nsel = (int)sh_n;
-  uint32_t kth;
-  if (nsel <= kRankBuf) {
-    int n2 = 1;
-    while (n2 < nsel) n2 <<= 1;
-    for (int i = nsel + tid; i < n2; i += kRankThreads) buf[i] = kPad;
-    __syncthreads();
-    block_sort<uint32_t, kRankThreads>(buf, n2);
-    kth = r <= nsel ? buf[r - 1] : kPad;
-  } else {
-    // exact MSD radix select (8 bits per pass) of the r-th smallest candidate key
-    if (tid == 0) {
-      sh_rem = (uint32_t)r;
-      sh_prefix = 0;
-    }
-    uint32_t mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (tid < 256) hist[tid] = 0;
-      __syncthreads();
-      const uint32_t prefix = sh_prefix;
-#pragma unroll
-      for (int e = 0; e < kRankPer; ++e)
-        if (key[e] <= T && (key[e] & mask) == prefix)
-          atomicAdd(&hist[(key[e] >> shift) & 255u], 1u);
-      __syncthreads();
-      if (tid == 0) {
-        uint32_t rem = sh_rem, dgt = 255;
-        for (uint32_t dd = 0; dd < 256; ++dd) {
-          if (hist[dd] >= rem) {
-            dgt = dd;
-            break;
-          }
-          rem -= hist[dd];
-        }
-        sh_rem = rem;
-        sh_prefix = prefix | (dgt << shift);
-      }
-      mask |= 255u << shift;
-      __syncthreads();
-    }
-    kth = sh_prefix;
-  }
-  if (tau && tid == 0) tau[q] = (kth == kPad) ? -__builtin_inff() : desc_key_to_score(kth);
 }
 
 // Tree merge of packed per-shard lists by bitonic networks: all P2 =
@@ -2952,7 +1953,6 @@ __global__ __launch_bounds__(kRefSortThreads) void refine_sort_kernel(RefineArgs
 // The exact top-k lies inside {fp32 >= B} (see the bound above), so the result is the fp64 evaluator's
 // for every query whose collected set fits kWideCap; a larger set keeps bit 1 (fp32 order).
 // ---------------------------------------------------------------------------
-constexpr int64_t kWideCap = 65536;
 constexpr int kWideThreads = 1024;
 constexpr int kWideSlice = 256;   // collected rows per work-group of wide_exact_kernel
 
@@ -3468,7 +2468,7 @@ __global__ void row_stats_init_kernel(uint32_t* stats) {
 // ---------------------------------------------------------------------------
 // Host-side planning and launch helpers.
 // ---------------------------------------------------------------------------
-struct TopkPlan {
+struct TopkPlan : PlanHead {   // (the head's offsets: off_tau .. off_part)
   int64_t n, k, nq, nq_pad;
   bool sample;        // false: n <= cap, dense scan of everything
   int64_t cap;        // FILTER capacity per query (or dense width when !sample)
@@ -3477,32 +2477,19 @@ struct TopkPlan {
   int64_t r;          // rank of the sampled score used as tau
   int64_t nchunk;     // kth_partial chunks per query
   int64_t kc;         // refine: candidates selected per query (>= k)
-  // workspace offsets (bytes)
-  size_t off_tau, off_cnt, off_keys, off_sample, off_part, off_cs, off_ci, off_delta, off_rcnt, total;
+  // workspace offsets (bytes) of the canonical-order stage, after the head
+  size_t off_cs, off_ci, off_delta, off_rcnt, total;
 };
 
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// Rows per query a threshold is set to let through over the whole corpus (the sample's r-th best score
-// stands for the target-th best of all rows); the hit lists hold 4x that (TopkPlan::cap).
-static int64_t hit_target(int64_t k) { return std::max<int64_t>(4096, 4 * k); }
-
-// Candidates the canonical-order stage selects per query: k plus a window for the entries within
-// 2 eps of the k-th score (a few on Gaussian data, <= 120 on the C2 leg's untrained-tower embeddings
-// at k = 1000, tools/c2_window_probe.py; up to 2048 in all).  A wider window goes to the wide resolve.
-static int64_t refine_width(int64_t k) { return std::min<int64_t>(kSelMaxK, k + std::max<int64_t>(256, k / 4)); }
-
-static size_t plan_refine_tail(TopkPlan& p, size_t o) {
+// The candidates of the canonical-order stage after the head: [nq_pad][kc] scores, ids, deltas, [nq_pad][2] counts.
+static size_t plan_refine_tail(TopkPlan& p) {
   p.kc = refine_width(p.k);
-  p.off_cs = o;
-  o = align_up(o + (size_t)p.nq_pad * p.kc * 4, 256);
-  p.off_ci = o;
-  o = align_up(o + (size_t)p.nq_pad * p.kc * 8, 256);
-  p.off_delta = o;
-  o = align_up(o + (size_t)p.nq_pad * p.kc * 4, 256);
-  p.off_rcnt = o;
-  o = align_up(o + (size_t)p.nq_pad * 8, 256);
-  return o;
+  WsBump b{p.head_end};
+  p.off_cs = b.take((size_t)p.nq_pad * p.kc * 4);
+  p.off_ci = b.take((size_t)p.nq_pad * p.kc * 8);
+  p.off_delta = b.take((size_t)p.nq_pad * p.kc * 4);
+  p.off_rcnt = b.take((size_t)p.nq_pad * 8);
+  return b.o;
 }
 
 static double poisson_tail_ge(double lam, int64_t r) {
@@ -3550,19 +2537,9 @@ static TopkPlan make_plan(int64_t nq, int64_t n, int64_t k) {
     if (p.m < r) p.m = std::min<int64_t>(n, r);
     p.nchunk = (p.m + kKthChunk - 1) / kKthChunk;
   }
-  size_t o = 0;
-  p.off_tau = o;
-  o = align_up(o + p.nq_pad * 4, 256);
-  p.off_cnt = o;
-  o = align_up(o + p.nq_pad * 4 * kCntStride, 256);
-  p.off_keys = o;
-  if (p.sample) o = align_up(o + (size_t)p.nq_pad * p.cap * 8, 256);
-  else o = align_up(o + (size_t)p.nq_pad * p.cap * 4, 256);
-  p.off_sample = o;
-  if (p.sample) o = align_up(o + (size_t)p.nq_pad * align_up(p.m, 4) * 4, 256);
-  p.off_part = o;
-  if (p.sample) o = align_up(o + (size_t)p.nq_pad * p.nchunk * p.r * 4, 256);
-  p.total = plan_refine_tail(p, o);
+  // filter hits are u64 keys, a dense scan's scores u32; without a sample m and nchunk are 0
+  static_cast<PlanHead&>(p) = plan_head_layout(p.nq_pad, p.cap, p.sample ? 8 : 4, p.m, p.nchunk * p.r);
+  p.total = plan_refine_tail(p);
   return p;
 }
 
@@ -3594,18 +2571,8 @@ static TopkPlan make_dist_plan(int64_t nq, int64_t n_local, int64_t n_global, in
     if (p.m > m_cap) p.m = m_cap;
     p.nchunk = (p.m + kKthChunk - 1) / kKthChunk;
   }
-  size_t o = 0;
-  p.off_tau = o;
-  o = align_up(o + p.nq_pad * 4, 256);
-  p.off_cnt = o;
-  o = align_up(o + p.nq_pad * 4 * kCntStride, 256);
-  p.off_keys = o;
-  o = align_up(o + (size_t)p.nq_pad * p.cap * 8, 256);
-  p.off_sample = o;
-  o = align_up(o + (size_t)p.nq_pad * align_up(p.m, 4) * 4, 256);
-  p.off_part = o;
-  o = align_up(o + (size_t)p.nq_pad * p.nchunk * p.r * 4, 256);
-  p.total = o;
+  static_cast<PlanHead&>(p) = plan_head_layout(p.nq_pad, p.cap, 8, p.m, p.nchunk * p.r);
+  p.total = p.head_end;
   return p;
 }
 
@@ -3702,10 +2669,6 @@ static int launch_scan_d(const ScanArgs& a, int mode, hipStream_t s) {
         if (gy > 1) {
           const dim3 grid32 = scan16_grid(a.nq, ntiles * kT16, kQueriesPerWG32);
           hipLaunchKernelGGL((ip_scan32r_kernel<D>), grid32, dim3(512), 0, s, a);
-        } else if (gy > 1) {
-          // not reached since the 32-query kernel took every launch of several blocks; dropping this arm
-          // takes the twelve ip_scan16r_kernel<D, false> out of the code object: a change of its own
-          hipLaunchKernelGGL((ip_scan16r_kernel<D, false>), grid, dim3(512), 0, s, a);
         } else {
           hipLaunchKernelGGL((ip_scan16r_kernel<D, true>), grid, dim3(512), 0, s, a);
         }
@@ -3752,30 +2715,9 @@ static int launch_scan(const ScanArgs& a, int d, int mode, hipStream_t s, int fa
   return rc;
 }
 
-static int launch_select(const SelectArgs& a, int input, int output, hipStream_t s) {
-  if (a.nq == 0) return DRT_OK;
-  dim3 grid((unsigned)a.nq);
-  const ProfPair pp = prof_begin(PROF_SELECT, s);
-  struct End { const ProfPair& p; hipStream_t s; ~End() { prof_end(p, s); } } end_{pp, s};
-  if (input == SEL_KEYS64 && output == SEL_TOPK)
-    hipLaunchKernelGGL((select_kernel<SEL_KEYS64, SEL_TOPK>), grid, dim3(kSelThreads), 0, s, a);
-  else if (input == SEL_DENSE32 && output == SEL_TOPK)
-    hipLaunchKernelGGL((select_kernel<SEL_DENSE32, SEL_TOPK>), grid, dim3(kSelThreads), 0, s, a);
-  else if (input == SEL_DENSE32 && output == SEL_KTH)
-    hipLaunchKernelGGL((select_kernel<SEL_DENSE32, SEL_KTH>), grid, dim3(kSelThreads), 0, s, a);
-  else
-    return DRT_EINVAL;
-  return hip_status(hipGetLastError());
-}
-
 static bool valid_dist_dims(int64_t nq, int64_t n_local, int64_t n_global, int32_t d, int32_t k) {
   return nq >= 0 && n_local >= 0 && n_global >= n_local && d > 0 && d % 64 == 0 && d <= 1024 && k >= 1 &&
          k <= kSelMaxK && n_global < (int64_t)0xFFFFFFFFll;
-}
-
-static bool valid_dims(int64_t nq, int64_t n, int32_t d, int32_t k) {
-  return nq >= 0 && n >= 0 && d > 0 && d % 64 == 0 && d <= 1024 && k >= 1 && k <= kSelMaxK &&
-         n < (int64_t)0xFFFFFFFFll;
 }
 
 }  // namespace drt
@@ -3895,26 +2837,14 @@ static int ip_topk_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
   if (rc) return rc;
   {
     const ProfPair pp = prof_begin(PROF_SELECT, s);
-    if (p.m <= kRankMaxKeys && p.r <= kRankBuf) {   // one launch: the whole sample row per work-group
-      // keys per thread sized to the sample (a sample of ~7k keys at 1M rows needs 8, not 80)
-      const uint32_t* smp = (const uint32_t*)(w + p.off_sample);
-      const int64_t ld = (int64_t)align_up(p.m, 4);
-      if (p.m <= (int64_t)kRankThreads * 8)
-        hipLaunchKernelGGL(kth_rank_kernel<8>, dim3((unsigned)nq), dim3(kRankThreads), 0, s, smp, ld, p.m, (int)p.r,
-                           tau, cnt);
-      else if (p.m <= (int64_t)kRankThreads * 24)
-        hipLaunchKernelGGL(kth_rank_kernel<24>, dim3((unsigned)nq), dim3(kRankThreads), 0, s, smp, ld, p.m, (int)p.r,
-                           tau, cnt);
-      else
-        hipLaunchKernelGGL(kth_rank_kernel<kRankPerMax>, dim3((unsigned)nq), dim3(kRankThreads), 0, s, smp, ld, p.m,
-                           (int)p.r, tau, cnt);
+    const uint32_t* smp = (const uint32_t*)(w + p.off_sample);
+    const int64_t ld = (int64_t)align_up(p.m, 4);
+    if (kth_rank_fits(p.m, p.r)) {   // one launch: the whole sample row per work-group
+      launch_kth_rank(nq, smp, ld, p.m, (int)p.r, tau, cnt, s);
     } else {
-      hipLaunchKernelGGL(kth_partial_kernel, dim3((unsigned)p.nchunk, (unsigned)nq), dim3(kKthThreads), 0, s,
-                         (const uint32_t*)(w + p.off_sample), (int64_t)align_up(p.m, 4), p.m, (int)p.r,
-                         (uint32_t*)(w + p.off_part));
-      hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, s,
-                         (const uint32_t*)(w + p.off_part), (int)p.nchunk, (int)p.r, (int64_t)p.r,
-                         (int64_t)(p.nchunk * p.r), tau, (uint32_t*)nullptr, cnt, (int)p.r);   // also zeroes the hit counters
+      launch_kth_partial(p.nchunk, nq, smp, ld, p.m, (int)p.r, (uint32_t*)(w + p.off_part), s);
+      launch_kth_final(nq, (const uint32_t*)(w + p.off_part), (int)p.nchunk, (int)p.r, (int64_t)p.r,
+                       (int64_t)(p.nchunk * p.r), tau, nullptr, cnt, (int)p.r, s);   // also zeroes the hit counters
     }
     prof_end(pp, s);
     DRT_CHECK_HIP(hipGetLastError());
@@ -4049,8 +2979,6 @@ int drt_refine_sort(const float* cand_s, const int64_t* cand_i, const float* del
   return hip_status(hipGetLastError());
 }
 
-static int64_t resolve_width(int64_t n) { return align_up(std::max<int64_t>(n, 4), 4); }
-
 // Dense exact rescan, chunked so the score buffer stays <= ~2 GB: queries per chunk.
 static int64_t resolve_chunk(int64_t nbad, int64_t n) {
   const int64_t width = resolve_width(n);
@@ -4058,14 +2986,9 @@ static int64_t resolve_chunk(int64_t nbad, int64_t n) {
   return std::min<int64_t>(chunk, kQueriesPerWG);
 }
 
-static size_t resolve_ws_bytes(int64_t chunk, int64_t n, int32_t d) {
-  return (size_t)(align_up(chunk * (int64_t)d * 2, 256) + align_up(chunk * resolve_width(n) * 4, 256) +
-                  align_up(chunk * 4, 256) + align_up(chunk * kSelMaxK * 16 + chunk * 8, 256));
-}
-
 size_t drt_ip_topk_resolve_workspace(int64_t nbad, int64_t n, int32_t d) {
   if (nbad <= 0 || n < 0 || d <= 0 || d % 64 || d > 1024) return 0;
-  return resolve_ws_bytes(resolve_chunk(nbad, n), n, d);
+  return resolve_layout(resolve_chunk(nbad, n), n, d).total;
 }
 
 }  // extern "C"
@@ -4091,19 +3014,19 @@ static int resolve_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
   // bytes holds the whole default chunk); nothing is allocated here
   const int64_t width = resolve_width(n);
   int64_t chunk = resolve_chunk((int64_t)bad.size(), n);
-  while (chunk > 1 && resolve_ws_bytes(chunk, n, d) > ws_bytes) chunk >>= 1;
-  DRT_REQUIRE(ws != nullptr && resolve_ws_bytes(chunk, n, d) <= ws_bytes);
+  while (chunk > 1 && resolve_layout(chunk, n, d).total > ws_bytes) chunk >>= 1;
   const bool refine = stats != nullptr && n > 0;
   const int64_t kc = refine_width(k);
+  const ResolveLayout l = resolve_layout(chunk, n, d, kc);
+  DRT_REQUIRE(ws != nullptr && l.total <= ws_bytes);
   char* wp = (char*)ws;
-  void* qbuf = wp;
-  void* sbuf = wp + align_up(chunk * (int64_t)d * 2, 256);
-  void* mbuf = (char*)sbuf + align_up(chunk * width * 4, 256);
-  char* rbuf = (char*)mbuf + align_up(chunk * 4, 256);   // refine: [chunk][kc] scores, ids, deltas; [chunk] cnt
-  float* rcs = (float*)rbuf;
-  int64_t* rci = (int64_t*)(rbuf + chunk * kc * 4);
-  float* rdl = (float*)(rbuf + chunk * kc * 12);
-  int32_t* rcn = (int32_t*)(rbuf + chunk * kc * 16);
+  void* qbuf = wp + l.qbuf;
+  void* sbuf = wp + l.scores;
+  void* mbuf = wp + l.qmap;
+  float* rcs = (float*)(wp + l.cand_s);
+  int64_t* rci = (int64_t*)(wp + l.cand_i);
+  float* rdl = (float*)(wp + l.delta);
+  int32_t* rcn = (int32_t*)(wp + l.cnt);
   int rc = DRT_OK;
   hipError_t e;
   for (size_t b0 = 0; b0 < bad.size() && rc == DRT_OK; b0 += chunk) {
@@ -4182,15 +3105,9 @@ static int resolve_impl(const void* Q, int64_t nq, const void* P, int64_t n, int
 
 extern "C" {
 
-static size_t wide_ws_bytes(int32_t d) {
-  const int64_t B = kQueriesPerWG;
-  return (size_t)(align_up(B * (int64_t)d * 2, 256) + align_up(B * 4, 256) + align_up(B * 4, 256) +
-                  align_up(B * kCntStride * 4, 256) + 2 * align_up(B * kWideCap * 8, 256));
-}
-
 size_t drt_ip_topk_resolve_wide_workspace(int64_t n, int32_t d) {
   if (n < 0 || d <= 0 || d % 64 || d > 1024) return 0;
-  return wide_ws_bytes(d);
+  return wide_layout(d).total;
 }
 
 int drt_ip_topk_resolve_wide(const void* Q, int64_t nq, const void* P, int64_t n, int32_t d, int32_t k,
@@ -4199,7 +3116,8 @@ int drt_ip_topk_resolve_wide(const void* Q, int64_t nq, const void* P, int64_t n
   DRT_REQUIRE(valid_dims(nq, n, d, k));
   if (n_resolved) *n_resolved = 0;
   if (nq == 0 || n == 0) return DRT_OK;
-  DRT_REQUIRE(Q && P && stats && out_scores && out_ids && status && ws && ws_bytes >= wide_ws_bytes(d));
+  const WideLayout l = wide_layout(d);
+  DRT_REQUIRE(Q && P && stats && out_scores && out_ids && status && ws && ws_bytes >= l.total);
   hipStream_t s = (hipStream_t)stream;
   std::vector<int32_t> st(nq);
   DRT_CHECK_HIP(hipMemcpyAsync(st.data(), status, nq * 4, hipMemcpyDeviceToHost, s));
@@ -4210,12 +3128,12 @@ int drt_ip_topk_resolve_wide(const void* Q, int64_t nq, const void* P, int64_t n
   if (wide.empty()) return DRT_OK;
   const int64_t B = kQueriesPerWG;
   char* wp = (char*)ws;
-  char* qbuf = wp;
-  int32_t* qmap = (int32_t*)(qbuf + align_up(B * (int64_t)d * 2, 256));
-  float* tau = (float*)((char*)qmap + align_up(B * 4, 256));
-  uint32_t* counts = (uint32_t*)((char*)tau + align_up(B * 4, 256));
-  uint64_t* keys = (uint64_t*)((char*)counts + align_up(B * kCntStride * 4, 256));
-  uint64_t* ekeys = (uint64_t*)((char*)keys + align_up(B * kWideCap * 8, 256));
+  char* qbuf = wp + l.qbuf;
+  int32_t* qmap = (int32_t*)(wp + l.qmap);
+  float* tau = (float*)(wp + l.tau);
+  uint32_t* counts = (uint32_t*)(wp + l.counts);
+  uint64_t* keys = (uint64_t*)(wp + l.keys);
+  uint64_t* ekeys = (uint64_t*)(wp + l.ekeys);
   for (size_t b0 = 0; b0 < wide.size(); b0 += B) {
     const int nb = (int)std::min<int64_t>(B, (int64_t)wide.size() - (int64_t)b0);
     for (int i = 0; i < nb; ++i)
@@ -4263,15 +3181,9 @@ int drt_ip_topk_resolve_wide(const void* Q, int64_t nq, const void* P, int64_t n
   return DRT_OK;
 }
 
-static size_t large_ws_bytes(int32_t d, int32_t k) {
-  const int64_t B = kQueriesPerWG;
-  return wide_ws_bytes(d) + (size_t)(2 * align_up(B * (int64_t)k * 8, 256) + 2 * align_up(B * (int64_t)k * 4, 256) +
-                                     align_up(B * 4, 256));
-}
-
 size_t drt_ip_topk_large_workspace(int32_t d, int32_t k) {
   if (d <= 0 || d % 64 || d > 1024 || k < 1 || k > kLargeMaxK) return 0;
-  return large_ws_bytes(d, k);
+  return large_layout(d, k).total;
 }
 
 int drt_ip_topk_large(const void* Q, int64_t nq, const void* P, int64_t n, int32_t d, int32_t k, int64_t id_offset,
@@ -4287,20 +3199,20 @@ int drt_ip_topk_large_keys(const void* Q, int64_t nq, const void* P, int64_t n, 
                            void* stream) {
   DRT_REQUIRE(nq >= 0 && n >= 0 && n < (int64_t)0xFFFFFFFFll && drt_ip_topk_large_workspace(d, k) > 0);
   if (nq == 0) return DRT_OK;
-  DRT_REQUIRE(Q && (P || n == 0) && stats && tau && out_scores && out_ids && status && ws &&
-              ws_bytes >= large_ws_bytes(d, k));
+  const LargeLayout l = large_layout(d, k);
+  DRT_REQUIRE(Q && (P || n == 0) && stats && tau && out_scores && out_ids && status && ws && ws_bytes >= l.total);
   hipStream_t s = (hipStream_t)stream;
   const int64_t B = kQueriesPerWG;
-  char* wp = (char*)ws + align_up(B * (int64_t)d * 2, 256) + align_up(B * 4, 256);   // (qbuf, qmap unused)
-  float* tauc = (float*)wp;
-  uint32_t* counts = (uint32_t*)((char*)tauc + align_up(B * 4, 256));
-  uint64_t* keys = (uint64_t*)((char*)counts + align_up(B * kCntStride * 4, 256));
-  uint64_t* ekeys = (uint64_t*)((char*)keys + align_up(B * kWideCap * 8, 256));
-  uint64_t* sel_k = (uint64_t*)((char*)ekeys + align_up(B * kWideCap * 8, 256));
-  uint32_t* sel_r = (uint32_t*)((char*)sel_k + align_up(B * (int64_t)k * 8, 256));
-  uint32_t* sel_n = (uint32_t*)((char*)sel_r + align_up(B * (int64_t)k * 4, 256));
-  uint64_t* bin_k = (uint64_t*)((char*)sel_n + align_up(B * 4, 256));
-  uint32_t* bin_r = (uint32_t*)((char*)bin_k + align_up(B * (int64_t)k * 8, 256));
+  char* wp = (char*)ws;
+  float* tauc = (float*)(wp + l.wide.tau);
+  uint32_t* counts = (uint32_t*)(wp + l.wide.counts);
+  uint64_t* keys = (uint64_t*)(wp + l.wide.keys);
+  uint64_t* ekeys = (uint64_t*)(wp + l.wide.ekeys);
+  uint64_t* sel_k = (uint64_t*)(wp + l.sel_k);
+  uint32_t* sel_r = (uint32_t*)(wp + l.sel_r);
+  uint32_t* sel_n = (uint32_t*)(wp + l.sel_n);
+  uint64_t* bin_k = (uint64_t*)(wp + l.bin_k);
+  uint32_t* bin_r = (uint32_t*)(wp + l.bin_r);
   for (int64_t b0 = 0; b0 < nq; b0 += B) {
     const int nb = (int)std::min<int64_t>(B, nq - b0);
     WideArgs w{};
@@ -4437,9 +3349,8 @@ int drt_ip_topk_dist_sample(const void* Q, int64_t nq, const void* P, int64_t n_
     int rc = launch_scan(a, d, SCAN_TOPR, s, PROF_SAMPLE);
     if (rc) return rc;
     const ProfPair pp = prof_begin(PROF_SELECT, s);
-    hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, s, (const uint32_t*)a.out,
-                       (int)nlists, (int)r, (int64_t)kTopRL, (int64_t)a.cap, (float*)nullptr, best,
-                       (uint32_t*)nullptr, kTopRL);
+    launch_kth_final(nq, (const uint32_t*)a.out, (int)nlists, (int)r, (int64_t)kTopRL, (int64_t)a.cap, nullptr, best,
+                     nullptr, kTopRL, s);
     prof_end(pp, s);
     return hip_status(hipGetLastError());
   }
@@ -4448,12 +3359,10 @@ int drt_ip_topk_dist_sample(const void* Q, int64_t nq, const void* P, int64_t n_
   if (rc) return rc;
   const ProfPair pp = prof_begin(PROF_SELECT, s);
   // fewer than r sampled rows: kth_partial pads its list with 0xFFFFFFFF
-  hipLaunchKernelGGL(kth_partial_kernel, dim3((unsigned)p.nchunk, (unsigned)nq), dim3(kKthThreads), 0, s,
-                     (const uint32_t*)(w + p.off_sample), (int64_t)align_up(p.m, 4), p.m, (int)r,
-                     (uint32_t*)(w + p.off_part));
-  hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, s,
-                     (const uint32_t*)(w + p.off_part), (int)p.nchunk, (int)r, (int64_t)r, (int64_t)(p.nchunk * r),
-                     (float*)nullptr, best, (uint32_t*)nullptr, (int)r);
+  launch_kth_partial(p.nchunk, nq, (const uint32_t*)(w + p.off_sample), (int64_t)align_up(p.m, 4), p.m, (int)r,
+                     (uint32_t*)(w + p.off_part), s);
+  launch_kth_final(nq, (const uint32_t*)(w + p.off_part), (int)p.nchunk, (int)r, (int64_t)r, (int64_t)(p.nchunk * r),
+                   nullptr, best, nullptr, (int)r, s);
   prof_end(pp, s);
   return hip_status(hipGetLastError());
 }
@@ -4463,9 +3372,8 @@ int drt_ip_topk_dist_tau(const uint32_t* lists, int64_t nq, int32_t nlists, int3
   DRT_REQUIRE(r > 0 && nq >= 0 && nlists >= 1 && (int64_t)nlists * r <= kKthChunk);
   if (nq == 0) return DRT_OK;
   DRT_REQUIRE(lists && tau);
-  hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, (hipStream_t)stream, lists,
-                     (int)nlists, (int)r, (int64_t)nq * r, (int64_t)r, tau, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                     (int)r);
+  launch_kth_final(nq, lists, (int)nlists, (int)r, (int64_t)nq * r, (int64_t)r, tau, nullptr, nullptr, (int)r,
+                   (hipStream_t)stream);
   return hip_status(hipGetLastError());
 }
 
@@ -4600,13 +3508,10 @@ int32_t drt_ip_topk_tighten_rank(int64_t n_local, int32_t npasses, int32_t k) {
   return 0;
 }
 
-// The distributed workspace plus [nq_pad][4] u32 of pass-0 state.
-static size_t passes_pass0_offset(const TopkPlan& p) { return align_up(p.total, 256); }
-static size_t passes_ws_bytes(const TopkPlan& p) { return passes_pass0_offset(p) + (size_t)p.nq_pad * 16; }
-
 size_t drt_ip_topk_filter_passes_workspace(int64_t nq, int64_t n_local, int64_t n_global, int32_t d, int32_t k) {
   if (!valid_dist_dims(nq, n_local, n_global, d, k)) return 0;
-  return passes_ws_bytes(make_dist_plan(nq, n_local, n_global, k));
+  const TopkPlan p = make_dist_plan(nq, n_local, n_global, k);
+  return passes_layout(p.total, p.nq_pad).total;
 }
 
 // dist_filter over a shard as `npasses` interleaved passes with ONE hit list and ONE select: pass p is
@@ -4629,7 +3534,8 @@ int drt_ip_topk_filter_passes(const void* Q, int64_t nq, const void* P, int64_t 
   FilterRun f;
   int rc = filter_setup(f, Q, nq, P, n_local, n_global, d, k, id_offset, tau, packed, ws, ws_bytes, stream);
   if (rc || nq == 0) return rc;
-  DRT_REQUIRE(ws_bytes >= passes_ws_bytes(f.p));
+  const PassesLayout pl = passes_layout(f.p.total, f.p.nq_pad);
+  DRT_REQUIRE(ws_bytes >= pl.total);
   if (r < 0) r = drt_ip_topk_tighten_rank(n_local, npasses, k);
   const int tall = (int)((n_local + kT16 - 1) / kT16);
   const bool tighten = r > 0 && n_local > 0 && pass_tiles(tall, npasses, 0) < tall;
@@ -4638,7 +3544,7 @@ int drt_ip_topk_filter_passes(const void* Q, int64_t nq, const void* P, int64_t 
     if (pass0_out) DRT_CHECK_HIP(hipMemsetAsync(pass0_out, 0, (size_t)nq * 16, f.s));
   }
   float* tau1 = tau1_out ? tau1_out : (float*)(f.w + f.p.off_tau);
-  uint32_t* pass0 = pass0_out ? pass0_out : (uint32_t*)(f.w + passes_pass0_offset(f.p));
+  uint32_t* pass0 = pass0_out ? pass0_out : (uint32_t*)(f.w + pl.off_pass0);
   if (n_local > 0) {
     if ((rc = filter_begin(f, true))) return rc;
     for (int ps = 0; ps < npasses; ++ps) {
@@ -4651,8 +3557,7 @@ int drt_ip_topk_filter_passes(const void* Q, int64_t nq, const void* P, int64_t 
       if ((rc = launch_scan(a, d, SCAN_FILTER, f.s, PROF_SCAN))) return rc;
       if (tighten && ps == 0) {
         const ProfPair pp = prof_begin(PROF_SELECT, f.s);
-        hipLaunchKernelGGL(tighten_kernel, dim3((unsigned)nq), dim3(kTightThreads), 0, f.s,
-                           (const uint64_t*)f.scan.out, f.p.cap, (const uint32_t*)f.cnt, tau, (int)r, tau1, pass0);
+        launch_tighten(nq, (const uint64_t*)f.scan.out, f.p.cap, f.cnt, tau, (int)r, tau1, pass0, f.s);
         prof_end(pp, f.s);
         DRT_CHECK_HIP(hipGetLastError());
       }
@@ -4685,9 +3590,8 @@ int drt_ip_topk_dist_filter_lists_at(const void* Q, int64_t nq, const void* P, i
   int rc = filter_setup(f, Q, nq, P, n_local, n_global, d, k, id_offset, lists, packed, ws, ws_bytes, stream);
   if (rc || nq == 0) return rc;
   float* tau = tau_out ? tau_out : (float*)(f.w + f.p.off_tau);
-  hipLaunchKernelGGL(kth_final_kernel, dim3((unsigned)nq), dim3(kKthThreads), 0, f.s, lists, (int)nlists, (int)r,
-                     lists_stride, (int64_t)r, tau, (uint32_t*)nullptr, n_local > 0 ? f.cnt : (uint32_t*)nullptr,
-                     (int)r);
+  launch_kth_final(nq, lists, (int)nlists, (int)r, lists_stride, (int64_t)r, tau, nullptr,
+                   n_local > 0 ? f.cnt : nullptr, (int)r, f.s);
   DRT_CHECK_HIP(hipGetLastError());
   if (n_local > 0) {
     if ((rc = filter_begin(f, false))) return rc;   // counters zeroed by the threshold kernel: no memset

@@ -66,7 +66,7 @@ def ip_topk(q: torch.Tensor, p: torch.Tensor, k: int, id_offset: int = 0, resolv
     return scores, ids, status
 
 
-MAX_K = 2048          # the candidate-list kernels' k (csrc/search.hip kSelMaxK)
+MAX_K = 2048          # the candidate-list kernels' k (csrc/search_internal.h kSelMaxK)
 MAX_K_LARGE = 32768   # the large-k path (drt_ip_topk_large)
 _WIDE_CAP = 65536     # rows one query of the large-k path may collect
 
