@@ -1,9 +1,11 @@
-// What search.hip and select.hip share, and the search workspace layouts.  Device code is not relocatable, so
-// a kernel is launched only from the unit that defines it: search.hip reaches select.hip's kernels through the
-// host launchers declared here.
+// What the units of the top-k search share -- search.hip (filter scan, planner, most entries), select.hip (select
+// and threshold kernels), refine.hip (canonical order, wide resolve, large k), merge.hip (list merges: the
+// constants only) -- and the search workspace layouts.  Device code is not relocatable, so a kernel is launched
+// only from the unit that defines it: the units reach each other's kernels through the host launchers here.
 #pragma once
 
 #include <algorithm>
+#include <vector>
 
 #include "drt_common.h"
 
@@ -69,6 +71,93 @@ DRT_INTERNAL void launch_kth_final(int64_t nq, const uint32_t* part, int nlists,
                                    hipStream_t s);
 DRT_INTERNAL void launch_tighten(int64_t nq, const uint64_t* keys, int64_t cap, const uint32_t* counts,
                                  const float* tau0, int r, float* tau1, uint32_t* pass0, hipStream_t s);
+
+// The scan kernels' argument (search.hip).  SCAN_TOPR: the grouped sample pass, see kTopRL there.
+enum { SCAN_FILTER = 0, SCAN_DENSE = 1, SCAN_TOPR = 2 };
+
+struct ScanArgs {
+  const __bf16* Q;
+  int64_t nq;
+  int64_t ldq;
+  const __bf16* P;
+  int64_t ldp;      // elements between consecutive corpus rows
+  int64_t row0;     // logical row i lives at P row (row0 + i * rstride)
+  int64_t nrows;
+  int64_t rstride;
+  const float* tau;   // FILTER: [nq] thresholds (NaN = inactive query)
+  uint32_t* counts;   // FILTER: hit counter of query q at counts[q * kCntStride] (zeroed by the caller)
+  void* out;          // FILTER: u64 [nq][cap] keys; DENSE: u32 [nq][cap] desc keys
+  int64_t cap;
+  int64_t exp_hits;   // FILTER: expected hits per query (0: cap / 4); picks the append flavour
+  uint32_t row_base;  // FILTER (lean kernels): added to the row of every hit key (a chunk of a longer shard)
+  // FILTER (lean kernels): an interleaved pass over the shard -- the launch covers the 16-row tiles t with
+  // t % npass == pass (npass <= 1: every tile); nrows stays the shard's row count, hit rows are shard rows
+  int32_t npass;
+  int32_t pass;
+};
+
+// The part of ScanArgs every launch shares: dense [nq, d] queries and [*, d] corpus rows, addressed as one
+// contiguous run from P's first row.  nrows and the mode's outputs are the caller's.
+static inline ScanArgs scan_args(const void* Q, int64_t nq, const void* P, int32_t d) {
+  ScanArgs a{};
+  a.Q = (const __bf16*)Q;
+  a.nq = nq;
+  a.ldq = d;
+  a.P = (const __bf16*)P;
+  a.ldp = d;
+  a.row0 = 0;
+  a.rstride = 1;
+  return a;
+}
+
+// A SCAN_FILTER launch over the n rows of P: hits >= tau[q] appended to out [nq][cap] through counts.
+static inline ScanArgs filter_scan_args(const void* Q, int64_t nq, const void* P, int32_t d, int64_t n,
+                                        const float* tau, uint32_t* counts, void* out, int64_t cap) {
+  ScanArgs a = scan_args(Q, nq, P, d);
+  a.nrows = n;
+  a.tau = tau;
+  a.counts = counts;
+  a.out = out;
+  a.cap = cap;
+  return a;
+}
+
+// search.hip: one scan launch (d picks the instantiation), timed under `family` (a ProfFamily, or -1).
+DRT_INTERNAL int launch_scan(const ScanArgs& a, int d, int mode, hipStream_t s, int family);
+
+// The canonical-order kernels' argument (refine.hip).
+struct RefineArgs {
+  const __bf16* Q;
+  int64_t nq;
+  int32_t d;
+  const __bf16* P;
+  int64_t n_local;
+  int64_t row_offset;
+  const float* cs;      // [nq][kc] fp32 scores, sorted desc (pads -FLT_MAX)
+  const int64_t* ci;    // [nq][kc] global ids (pads -1)
+  int32_t kc, k;
+  const float* stats;   // row statistics (drt_row_stats_bf16)
+  const float* tau;     // [nq] filter thresholds or NULL (every row was scored)
+  float* delta;         // [nq][kc]
+  int32_t* cnt;         // [nq][2]: window size C (-1: exact in fp32, -2: window wider than the list), eps bits
+  int32_t* status;      // [nq] (indexed through qmap) or NULL
+  const int32_t* qmap;  // output row of query q, or NULL
+  bool set_status;      // status[row] = this stage's bits (the exact rescan clears it) instead of |=
+  int32_t slice;        // refine_delta: candidates per work-group (64 or 256; 0 = kRefSlice)
+  float* out_s;         // refine_sort: [*, k]
+  int64_t* out_i;
+};
+
+// refine.hip.  launch_refine: the one-GPU canonical order of nq candidate lists (PROF_SELECT).  The dense and
+// the wide resolve pick their queries with flagged_queries -- status [nq] read back (synchronises s), `out` =
+// the q with (status[q] & mask) == want -- and gather a chunk of them with gather_queries: rows idx[0 .. nb) of
+// Q [*, d] into qbuf, one device-to-device copy each, and idx into the device array qmap (the chunk's output
+// rows).  Both return the first failing HIP call's status.
+DRT_INTERNAL int launch_refine(RefineArgs& ra, hipStream_t s);
+DRT_INTERNAL int flagged_queries(const int32_t* status, int64_t nq, int32_t mask, int32_t want, hipStream_t s,
+                                 std::vector<int32_t>& out);
+DRT_INTERNAL int gather_queries(const void* Q, int32_t d, const int32_t* idx, int64_t nb, void* qbuf, void* qmap,
+                                hipStream_t s);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -222,7 +222,7 @@ def _kth_bound(q: torch.Tensor, p: torch.Tensor, k: int, stats: torch.Tensor) ->
     order): the k-th largest of the queries' dense fp32 scores (MFMA GEMM, gemm_nt_f32, over row
     blocks, running top-k values), lowered by a bound on any fp32 summation of the d exact bf16 x bf16
     products -- 1.1 d u ||q|| max ||p||, above both the classic gamma_(d-1) bound and the scan's measured
-    MFMA-chain bound (10 u per 32-term step, csrc/search.hip "Error bound") -- so k rows' exact sums lie
+    MFMA-chain bound (10 u per 32-term step, csrc/refine.hip "Error bound") -- so k rows' exact sums lie
     above it.  Dense work for the (rare) queries that need it only."""
     nq, d = q.shape
     best = None
@@ -265,7 +265,7 @@ def resolve_wide(q, p, k, id_offset, scores, ids, status, stats: torch.Tensor, n
 def row_stats(p: torch.Tensor, prev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[ROW_STATS_LEN] fp32 device tensor: (max squared row norm, 1.0 if every element is an integer,
     then per 32-element k-step t the max squared norm of the row prefixes [0, 32 (t + 1))) of the bf16
-    rows p [n, d] -- the error bound of the scan's MFMA chain (csrc/search.hip) -- combined with
+    rows p [n, d] -- the error bound of the scan's MFMA chain (csrc/refine.hip "Error bound") -- combined with
     ``prev`` (the stats of earlier rows) when given."""
     _require_device(p)
     return ops.load().row_stats(p, prev)

@@ -85,7 +85,7 @@ int drt_ip_topk_resolve(const void* Q, int64_t nq, const void* P, int64_t n, int
  * drt_row_stats_bf16: stats[DRT_ROW_STATS_LEN] (device floats) = (max squared L2 norm over the rows,
  *   1.0f while every element is an integer, then for each 32-element k-step t < ceil(d / 32) the max
  *   over the rows of the squared norm of the prefix [0, 32 (t + 1))) -- the error bound of the scan's
- *   MFMA chain (csrc/search.hip, "Error bound"); accumulate = 0 (re)initialises, 1 combines with the
+ *   MFMA chain (csrc/refine.hip, "Error bound"); accumulate = 0 (re)initialises, 1 combines with the
  *   stats already there (appended rows).  Across shards combine by max (the flag by min).  Reads
  *   every row once.  d <= 1024.
  * drt_ip_topk_exact_bf16: drt_ip_topk_bf16 in the canonical order (same workspace).  status bit 0

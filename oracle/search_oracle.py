@@ -291,13 +291,13 @@ def merge_packed(parts, k, n_global, k_cert=None):
 
 
 # ---------------------------------------------------------------------------
-# Sharded search at k > 2048 (csrc/search.hip drt_ip_topk_large_keys + drt_merge_exact, round 6): every
+# Sharded search at k > 2048 (csrc/refine.hip drt_ip_topk_large_keys + drt_merge_exact, round 6): every
 # shard's canonical top-k carries each entry's EXACT order key; the lists are merged by (key, global id).
 # Like the protocol above this only restates the exchanged data; the tests check the end result against
 # the single-index ip_topk.
 # ---------------------------------------------------------------------------
 def desc_key64(scores: np.ndarray) -> np.ndarray:
-    """uint64 whose ascending order is descending fp64 score (search.hip desc_key64)."""
+    """uint64 whose ascending order is descending fp64 score (refine.hip desc_key64)."""
     s = np.asarray(scores, dtype=np.float64) + 0.0
     u = s.view(np.uint64)
     neg = (u >> np.uint64(63)) != 0

@@ -43,7 +43,7 @@ def _np_stats(p):
 
 
 def _np_eps(q, p):
-    """The scan's certified fp32 error bound per query (csrc/search.hip "Error bound", refine_eps):
+    """The scan's certified fp32 error bound per query (csrc/refine.hip "Error bound", refine_eps):
     10 u (1 + 1e-3) (sum_{t=1}^{T-1} ||q_[0,32t)|| max ||p_[0,32t)|| + ||q|| max ||p||)."""
     _, _, pref = _np_stats(p)
     q64 = q.astype(np.float64)
@@ -295,6 +295,93 @@ def test_exact_order_degenerate_near_ties_bit_exact(dev, grouped):
     np.testing.assert_array_equal(torch.cat([r[1] for r in res]).cpu().numpy(), ei)
     _assert_scores(torch.cat([r[0] for r in res]).cpu().numpy(), es)
     assert idx.order_uncertified == 0 and idx.wide_resolved == nq
+
+
+_SCATTER = dict(nq=300, n=12000, d=128, k=100, id_offset=7)   # n <= the plan's cap: dense path, every query certified
+_scatter_cache = {}
+
+
+def _scatter_case(kind):
+    """(q, p, oracle scores, oracle ids) of the scattered-subset tests, computed once and read-only."""
+    if kind not in _scatter_cache:
+        c = _SCATTER
+        rng = np.random.default_rng(31 if kind == "int" else 32)
+        make = (lambda shape: int_bf16(rng, shape, -4, 4)) if kind == "int" else (lambda shape: gauss_bf16(rng, shape))
+        q, p = make((c["nq"], c["d"])), make((c["n"], c["d"]))
+        es, ei = orc.ip_topk(q, p, c["k"], id_offset=c["id_offset"])
+        for a in (q, p, es, ei):
+            a.setflags(write=False)
+        _scatter_cache[kind] = (q, p, es, ei)
+    return _scatter_cache[kind]
+
+
+def _scatter_start(dev, kind, with_stats):
+    """ip_topk without resolve on a scatter case: every query certified; returns the device tensors, a copy
+    of the outputs and the flagged rows (the odd queries: 150 of them, chunks of 128 + 22, none adjacent)."""
+    import torch
+    from denseretrievaltoolkits_amd import kernels
+    c = _SCATTER
+    q, p, es, ei = _scatter_case(kind)
+    qt, pt = to_dev_bf16(q, dev), to_dev_bf16(p, dev)
+    stats = kernels.row_stats(pt) if with_stats else None
+    s, i, st = kernels.ip_topk(qt, pt, c["k"], id_offset=c["id_offset"], resolve=False, stats=stats)
+    torch.cuda.synchronize()
+    assert (st.cpu().numpy() == 0).all()
+    flagged = torch.arange(1, c["nq"], 2, device=dev)
+    assert flagged.numel() == 150
+    return qt, pt, stats, s, i, st, s.clone(), i.clone(), flagged
+
+
+def _assert_unflagged_untouched(s, i, s0, i0):
+    import torch
+    assert torch.equal(s[0::2], s0[0::2]) and torch.equal(i[0::2], i0[0::2])
+
+
+@pytest.mark.parametrize("kind", ["int", "gauss"])
+def test_resolve_scattered_subset(dev, kind):
+    """The dense rescan of a flagged subset that is neither everything nor contiguous and spans two
+    128-query chunks: integer data without statistics (exact fp32 scores, ties by id) and Gaussian data in
+    the canonical order.  The flagged rows are rebuilt from junk, the others are not touched."""
+    import torch
+    from denseretrievaltoolkits_amd import kernels
+    c = _SCATTER
+    _, _, es, ei = _scatter_case(kind)
+    if kind == "int":   # the case is about ties: many equal scores inside the oracle's top-k rows
+        assert (np.diff(es, axis=1) == 0).mean() > 0.2
+    qt, pt, stats, s, i, st, s0, i0, flagged = _scatter_start(dev, kind, kind == "gauss")
+    s[flagged] = -12345.0
+    i[flagged] = -99
+    st[flagged] = 1
+    assert kernels.resolve_failed(qt, pt, c["k"], c["id_offset"], s, i, st, stats=stats) == 150
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(i.cpu().numpy(), ei)
+    if kind == "int":
+        np.testing.assert_array_equal(s.cpu().numpy(), es)
+    else:
+        _assert_scores(s.cpu().numpy(), es)
+    _assert_unflagged_untouched(s, i, s0, i0)
+    assert (st.cpu().numpy() == 0).all()
+
+
+def test_resolve_wide_scattered_subset(dev):
+    """The wide resolve of the same scattered subset (status 2 set by hand): each flagged row is rebuilt
+    from its k-th fp32 score alone -- the one entry wide_prep_kernel reads -- and the rest left as it was."""
+    import torch
+    from denseretrievaltoolkits_amd import kernels
+    c = _SCATTER
+    _, _, es, ei = _scatter_case("gauss")
+    qt, pt, stats, s, i, st, s0, i0, flagged = _scatter_start(dev, "gauss", True)
+    kth = s[flagged, c["k"] - 1].clone()
+    s[flagged] = -12345.0
+    s[flagged, c["k"] - 1] = kth
+    i[flagged] = -99
+    st[flagged] = 2
+    assert kernels.resolve_wide(qt, pt, c["k"], c["id_offset"], s, i, st, stats) == 150
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(i.cpu().numpy(), ei)
+    _assert_scores(s.cpu().numpy(), es)
+    _assert_unflagged_untouched(s, i, s0, i0)
+    assert (st.cpu().numpy() == 0).all()
 
 
 @pytest.mark.parametrize("row_offset", [0, 5000])

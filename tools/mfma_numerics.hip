@@ -1,6 +1,6 @@
 // Diagnostic (tools/mfma_numerics.py): what one v_mfma_f32_16x16x32_bf16 and a chain of them
 // compute, bit for bit -- the summation semantics the canonical-order error bound rests on
-// (csrc/search.hip, refine_eps).  One wave per trial: acc = C; for s < S: acc = mfma(A_s, B_s, acc).
+// (csrc/refine.hip, refine_eps).  One wave per trial: acc = C; for s < S: acc = mfma(A_s, B_s, acc).
 // Layout (host side restates it): A [T][S][16 m][32 k], B [T][S][16 n][32 k] (bf16 bits),
 // C / D [T][16 m][16 n] fp32.  Lane l holds A[m = l % 16][k = 8 (l / 16) + e], B[n = l % 16][same k],
 // D[m = 4 (l / 16) + i][n = l % 16].

@@ -8,7 +8,7 @@ inputs and compares every output with candidate summation models of D = C + sum_
   tree_rn    the 32 products summed pairwise in fp32, then + C
 Then chains of S = 24 steps (d = 768, the scan's accumulation) against the per-step models, and the
 worst error of the hardware chain against the exact sum, in units of u * sum |a b| (u = 2^-24) and of
-u * sum_t |partial sum t| -- the quantities the bound of csrc/search.hip refine_eps is built from.
+u * sum_t |partial sum t| -- the quantities the bound of csrc/refine.hip refine_eps is built from.
 Prints one JSON object.
 """
 import ctypes
