@@ -8,6 +8,7 @@
 //   faiss.IndexFlatIP.search           DRT/evaluator/index.py:31-33        drt::ip_topk(+_resolve)
 //   per-partition merge                DRT/model/utils.py:215-229          drt::topk_merge, merge_packed
 //   corpus sharding (file exchange)    DRT/trainer/trainer.py:191-262      drt::dist_sample/_tau/_filter
+//   hard-negative skip loop            DRT/trainer/sampler.py:69-80        drt::topk_exclude, pair_scores
 //   score matrix + CE (+ autograd)     DRT/model/biencoder.py:107-119      drt::score_ce_fwd/_bwd
 //   HF BertModel forward pieces        transformers modeling_bert.py       drt::embed_ln, linear,
 //                                                                          attention, layernorm, pool,
@@ -518,6 +519,79 @@ std::tuple<Tensor, Tensor, Tensor> merge_packed(const Tensor& parts_, int64_t k,
   return {s, i, st};
 }
 
+// ---------------------------------------------------------------------------- hard-negative mining
+// Stable compaction of a canonical top-k list [nq, k_in] (drt_topk_exclude): drops pads, ids in the query's
+// sorted segment excl[excl_off[q] .. excl_off[q + 1]) and entries at or above ceiling[q]; survivors skip ..
+// skip + k_out - 1 -> (scores, ids) [nq, k_out], count [nq] = survivors before skip / k_out.  excl_off holds
+// absolute offsets into excl (a view of a longer offset vector is fine); its monotonicity is the caller's
+// (checking it would synchronise).
+std::tuple<Tensor, Tensor, Tensor> topk_exclude(const Tensor& scores_, const Tensor& ids_, const Tensor& excl_,
+                                                const Tensor& excl_off_, const c10::optional<Tensor>& ceiling_,
+                                                int64_t skip, int64_t k_out) {
+  need(scores_, "scores", at::kFloat, 2);
+  need(ids_, "ids", at::kLong, 2);
+  need(excl_, "excl", at::kLong, 1);
+  need(excl_off_, "excl_off", at::kLong, 1);
+  TORCH_CHECK_VALUE(scores_.sizes() == ids_.sizes(), "topk_exclude: scores ", scores_.sizes(), " and ids ",
+                    ids_.sizes(), " differ in shape");
+  TORCH_CHECK_VALUE(ids_.device() == scores_.device() && excl_.device() == scores_.device() &&
+                        excl_off_.device() == scores_.device(),
+                    "topk_exclude: every tensor must be on the scores' device ", scores_.device());
+  const int64_t nq = scores_.size(0), k_in = scores_.size(1);
+  TORCH_CHECK_VALUE(excl_off_.numel() == nq + 1, "excl_off: expected ", nq + 1, " offsets (nq + 1), got ",
+                    excl_off_.numel());
+  TORCH_CHECK_VALUE(k_out >= 1 && skip >= 0 && skip <= 0x7FFFFFFF && k_out <= 0x7FFFFFFF,
+                    "topk_exclude: unsupported skip=", skip, " k_out=", k_out, " (skip >= 0, k_out >= 1)");
+  TORCH_CHECK_VALUE(k_in >= 1 && k_in <= 32768, "topk_exclude: unsupported list length k_in=", k_in,
+                    " (1 <= k_in <= 32768)");
+  const c10::DeviceGuard g(scores_.device());
+  const Tensor scores = scores_.contiguous(), ids = ids_.contiguous(), excl = excl_.contiguous(),
+               excl_off = excl_off_.contiguous();
+  Tensor ceiling;
+  if (ceiling_.has_value()) {
+    need(*ceiling_, "ceiling", at::kFloat, 1);
+    TORCH_CHECK_VALUE(ceiling_->device() == scores.device() && ceiling_->numel() == nq,
+                      "ceiling: expected a float [", nq, "] tensor on ", scores.device());
+    ceiling = ceiling_->contiguous();
+  }
+  Tensor os = at::empty({nq, k_out}, scores.options());
+  Tensor oi = at::empty({nq, k_out}, ids.options());
+  Tensor cnt = at::empty({nq}, scores.options().dtype(at::kInt));
+  if (nq == 0) return {os, oi, cnt};
+  check_rc(drt_topk_exclude(scores.data_ptr<float>(), ids.data_ptr<int64_t>(), nq, (int32_t)k_in,
+                            excl.numel() ? excl.data_ptr<int64_t>() : nullptr, excl_off.data_ptr<int64_t>(),
+                            ceiling.defined() ? ceiling.data_ptr<float>() : nullptr, (int32_t)skip, (int32_t)k_out,
+                            os.data_ptr<float>(), oi.data_ptr<int64_t>(), cnt.data_ptr<int32_t>(), stream_of(scores)),
+           "drt_topk_exclude");
+  return {os, oi, cnt};
+}
+
+// exact scores (fp64 sums rounded to fp32) of the pairs (query qidx[j], row rows[j] of p); -FLT_MAX for a
+// row outside p (drt_pair_scores_bf16)
+Tensor pair_scores(const Tensor& q_, const Tensor& p_, const Tensor& qidx_, const Tensor& rows_) {
+  need(q_, "q", at::kBFloat16, 2);
+  need(p_, "p", at::kBFloat16, 2);
+  need(qidx_, "qidx", at::kInt, 1);
+  need(rows_, "rows", at::kLong, 1);
+  TORCH_CHECK_VALUE(q_.size(1) == p_.size(1), "q and p differ in dimension: ", q_.sizes(), " vs ", p_.sizes());
+  TORCH_CHECK_VALUE(p_.device() == q_.device() && qidx_.device() == q_.device() && rows_.device() == q_.device(),
+                    "pair_scores: every tensor must be on the queries' device ", q_.device());
+  TORCH_CHECK_VALUE(qidx_.numel() == rows_.numel(), "pair_scores: ", qidx_.numel(), " query indices for ",
+                    rows_.numel(), " rows");
+  const int64_t d = q_.size(1);
+  TORCH_CHECK_VALUE(d >= 8 && d % 8 == 0 && d <= 1024, "pair_scores: unsupported d=", d, " (d % 8 == 0, d <= 1024)");
+  const c10::DeviceGuard g(q_.device());
+  const Tensor q = q_.contiguous(), p = p_.contiguous(), qidx = qidx_.contiguous(), rows = rows_.contiguous();
+  const int64_t npairs = rows.numel();
+  Tensor out = at::empty({npairs}, q.options().dtype(at::kFloat));
+  if (npairs == 0) return out;
+  check_rc(drt_pair_scores_bf16(q.size(0) ? q.data_ptr() : nullptr, q.size(0), p.size(0) ? p.data_ptr() : nullptr,
+                                p.size(0), (int32_t)d, qidx.data_ptr<int32_t>(), rows.data_ptr<int64_t>(), npairs,
+                                out.data_ptr<float>(), stream_of(q)),
+           "drt_pair_scores_bf16");
+  return out;
+}
+
 // ---------------------------------------------------------------------------- training loss
 std::tuple<Tensor, Tensor, Tensor> score_ce_fwd(const Tensor& q_, const Tensor& p_, int64_t target_stride,
                                                 double scale) {
@@ -695,6 +769,9 @@ TORCH_LIBRARY(drt, m) {
   m.def("filter_passes_into(Tensor q, Tensor p, int n_global, int k, int id_offset, Tensor tau, int npasses, int r, "
         "Tensor(a!) packed, Tensor(b!)? tau1=None, Tensor(c!)? pass0=None) -> ()");
   m.def("merge_packed(Tensor parts, int k, int n_global, int k_cert=-1) -> (Tensor, Tensor, Tensor)");
+  m.def("topk_exclude(Tensor scores, Tensor ids, Tensor excl, Tensor excl_off, Tensor? ceiling, int skip, int k_out) -> "
+        "(Tensor, Tensor, Tensor)");
+  m.def("pair_scores(Tensor q, Tensor p, Tensor qidx, Tensor rows) -> Tensor");
   m.def("score_ce_fwd(Tensor q, Tensor p, int target_stride, float scale) -> (Tensor, Tensor, Tensor)");
   m.def("score_ce_bwd(Tensor grad, Tensor q, Tensor p, Tensor scores, Tensor lse, int target_stride, "
         "float scale) -> (Tensor, Tensor)");
@@ -728,6 +805,8 @@ TORCH_LIBRARY_IMPL(drt, CUDA, m) {   // the GPU dispatch key of torch-ROCm
   m.impl("dist_filter_lists_into", &dist_filter_lists_into);
   m.impl("dist_filter_into", &dist_filter_into);
   m.impl("merge_packed", &merge_packed);
+  m.impl("topk_exclude", &topk_exclude);
+  m.impl("pair_scores", &pair_scores);
   m.impl("score_ce_fwd", &score_ce_fwd);
   m.impl("score_ce_bwd", &score_ce_bwd);
   m.impl("embed_ln", &embed_ln);

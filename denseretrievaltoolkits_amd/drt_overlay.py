@@ -24,6 +24,9 @@ HOT_PATH_MODULES = {
     "DRT.evaluator.metrics": "denseretrievaltoolkits_amd.evaluator.metrics",
     "DRT.trainer.trainer": "denseretrievaltoolkits_amd.trainer.trainer",
     "DRT.trainer.losses": "denseretrievaltoolkits_amd.trainer.losses",
+    # dense hard-negative mining (no counterpart file in the reference: DenseNegatives stands beside
+    # BM25Negatives of DRT/trainer/sampler.py, which keeps resolving to the user's package)
+    "DRT.trainer.mining": "denseretrievaltoolkits_amd.trainer.mining",
 }
 
 

@@ -41,22 +41,38 @@ class BaseFaissIPRetriever:
     def add(self, p_reps) -> None:
         self.index.add(p_reps)
 
-    def search(self, q_reps, k: int = 1000) -> np.ndarray:
-        scores, indices = self.index.search(q_reps, k)
-        self.last_scores = scores
-        return indices
+    def search(self, q_reps, k: int = 1000, exclude=None) -> np.ndarray:
+        """``exclude``: a sequence of per-query id sequences (or None) -- query j's result is then the
+        top-k of the rows NOT in ``exclude[j]``, exactly (FlatIPIndex.search_filtered_device; the skip
+        loop of BM25Negatives.load_passages, DRT/trainer/sampler.py:69-80, without its over-fetch
+        guess).  Rows short of k hits are padded -1."""
+        if exclude is None:
+            scores, indices = self.index.search(q_reps, k)
+            self.last_scores = scores
+            return indices
+        return self.batch_search(q_reps, k, max(1, q_reps.shape[0]), exclude=exclude)
 
     def search_device(self, q_reps, k: int = 1000):
         """Device tensors (scores fp32, ids int64) without the host round trip."""
         return self.index.search_device(q_reps, k)
 
-    def batch_search(self, q_reps, k: int, batch_size: int, quiet: bool = False) -> np.ndarray:
+    def batch_search(self, q_reps, k: int, batch_size: int, quiet: bool = False, exclude=None) -> np.ndarray:
         """All query batches enqueued back to back (FlatIPIndex.search_batches_iter: batch j + 1 is
-        on the GPU while batch j is certified and its results land in pinned host memory)."""
+        on the GPU while batch j is certified and its results land in pinned host memory).
+        ``exclude``: per-query id sequences to leave out (see ``search``)."""
         n = q_reps.shape[0]
         if n == 0:
             return np.zeros((0, k), dtype=np.int64)
         qd = self.index._queries(q_reps)
+        if exclude is not None:
+            from ..trainer.mining import build_exclusions
+            if len(exclude) != n:
+                raise ValueError(f"exclude holds {len(exclude)} id lists for {n} queries")
+            excl, excl_off = build_exclusions(exclude, self.index.device)
+            res = list(self.index.search_filtered_batches_iter(
+                [qd[a: a + batch_size] for a in range(0, n, batch_size)], k, excl, excl_off, to_host=True))
+            self.last_scores = np.concatenate([r[0] for r in res])
+            return np.concatenate([r[1] for r in res])
         res = list(self.index.search_batches_iter([qd[a: a + batch_size] for a in range(0, n, batch_size)], k,
                                                   to_host=True))
         self.last_scores = np.concatenate([r[0] for r in res])

@@ -412,6 +412,46 @@ def exchange_cap(kc: int, nparts: int) -> int:
     return kc if cap * 10 >= kc * 9 else cap
 
 
+def filtered_depth(k: int, skip: int, max_excluded: int) -> int:
+    """Search depth K at which a filtered top-k is exact: the first skip + k survivors of the top-K list are
+    the top-(skip + k) of the corpus minus a query's excluded set E whenever K >= skip + k + |E| (at most
+    |E| entries of the list are dropped), so K = skip + k + max_q |E_q|.  Beyond the large-k path's
+    MAX_K_LARGE there is no exact answer to give: ValueError."""
+    if k < 1 or skip < 0 or max_excluded < 0:
+        raise ValueError(f"filtered search needs k >= 1, skip >= 0 (k={k}, skip={skip})")
+    depth = skip + k + max_excluded
+    if depth > MAX_K_LARGE:
+        raise ValueError(f"filtered search depth skip + k + max exclusions = {skip} + {k} + {max_excluded} = {depth} "
+                         f"exceeds the limit {MAX_K_LARGE} (MAX_K_LARGE)")
+    return depth
+
+
+def topk_exclude(scores: torch.Tensor, ids: torch.Tensor, excl: torch.Tensor, excl_off: torch.Tensor,
+                 k_out: int, skip: int = 0,
+                 ceiling: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Stable compaction of canonical top-k lists [nq, k_in] (k_in <= 32768): query q drops pads, the ids in
+    its sorted segment ``excl[excl_off[q]:excl_off[q + 1]]`` (int64; ``excl_off`` [nq + 1], absolute offsets
+    into ``excl``) and, with ``ceiling`` [nq] fp32, entries scoring >= ceiling[q].  Returns the survivors
+    skip .. skip + k_out - 1 in their input order, (scores fp32, ids int64) [nq, k_out] padded
+    (-FLT_MAX, -1), and count int32 [nq] = the survivors before ``skip`` / ``k_out`` apply."""
+    _require_device(scores, ids, excl, excl_off)
+    if ceiling is not None:
+        _require_device(ceiling)
+    if scores.dim() != 2 or scores.shape != ids.shape:
+        raise ValueError("topk_exclude expects [nq, k_in] scores and ids")
+    return ops.load().topk_exclude(scores, ids, excl, excl_off, ceiling, skip, k_out)
+
+
+def pair_scores(q: torch.Tensor, p: torch.Tensor, qidx: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """fp32 [npairs]: the exact score (fp64 sum of the bf16 products, rounded once -- what the canonical
+    search reports) of query ``qidx[j]`` (int32) against row ``rows[j]`` (int64) of ``p``; -FLT_MAX for a
+    row outside ``p`` (a shard answers for its own rows)."""
+    _require_device(q, p, qidx, rows)
+    if q.dtype != torch.bfloat16 or p.dtype != torch.bfloat16:
+        raise ValueError("pair_scores expects bf16 queries and corpus")
+    return ops.load().pair_scores(q, p, qidx.to(torch.int32), rows.to(torch.int64))
+
+
 def gemm_nt_f32(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C = a @ b.T with bf16 inputs and fp32 accumulation/output (MFMA)."""
     lib = _native.load()

@@ -14,6 +14,8 @@ formula of the fused score + cross-entropy op.
     torch.ops.drt.dist_sample / dist_tau / dist_filter / dist_filter_chunks_into / dist_filter_lists / merge_packed
                                                                                             (sharded, §8e)
     torch.ops.drt.filter_passes_into   (one GPU's group filter: interleaved passes, tightened threshold)
+    torch.ops.drt.topk_exclude(scores, ids, excl, excl_off, ceiling, skip, k_out) -> (scores, ids, count)
+    torch.ops.drt.pair_scores(q, p, qidx, rows)         -> scores                  sampler.py:69-80 (mining)
     torch.ops.drt.score_ce_fwd(q, p, stride, scale)     -> (loss, scores, lse)     biencoder.py:107-119
     torch.ops.drt.score_ce_bwd(g, q, p, scores, lse, stride, scale) -> (dq, dp)
     torch.ops.drt.embed_ln / linear / attention / layernorm / pool / l2_normalize  (BertModel pieces)
@@ -147,6 +149,16 @@ def _register_python_parts():
         nq = parts.shape[1]
         return (parts.new_empty((nq, k), dtype=torch.float32), parts.new_empty((nq, k), dtype=torch.int64),
                 parts.new_empty((nq,), dtype=torch.int32))
+
+    @lib.register_fake("drt::topk_exclude")
+    def _(scores, ids, excl, excl_off, ceiling, skip, k_out):
+        nq = scores.shape[0]
+        return (scores.new_empty((nq, k_out), dtype=torch.float32), ids.new_empty((nq, k_out), dtype=torch.int64),
+                scores.new_empty((nq,), dtype=torch.int32))
+
+    @lib.register_fake("drt::pair_scores")
+    def _(q, p, qidx, rows):
+        return q.new_empty((rows.shape[0],), dtype=torch.float32)
 
     @lib.register_fake("drt::score_ce_fwd")
     def _(q, p, target_stride, scale):

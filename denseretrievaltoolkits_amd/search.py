@@ -314,6 +314,45 @@ def _gtau_finish_group(pend, redo, wide=None):
     return res, nredo, nunc
 
 
+def filtered_depth(k: int, skip: int, excl_off: torch.Tensor, ntotal: int, depth: Optional[int] = None) -> int:
+    """Search depth of a filtered search (kernels.filtered_depth: K = skip + k + the longest exclusion
+    segment, ValueError past MAX_K_LARGE), raised to ``depth`` when the caller asks for more (a score
+    ceiling drops an unknown number of entries) and cut at the corpus size (a list of every row is exact
+    at any depth).  Reads the segment lengths back once (synchronises)."""
+    if excl_off.dim() != 1 or excl_off.numel() < 1:
+        raise ValueError("excl_off must be a 1-d tensor of nq + 1 offsets")
+    longest = int((excl_off[1:] - excl_off[:-1]).max().item()) if excl_off.numel() > 1 else 0
+    need = kernels.filtered_depth(k, skip, max(0, longest))
+    if depth is not None:
+        if depth > kernels.MAX_K_LARGE:
+            raise ValueError(f"filtered search depth {depth} exceeds the limit {kernels.MAX_K_LARGE} (MAX_K_LARGE)")
+        need = max(need, int(depth))
+    return max(1, min(need, int(ntotal)))
+
+
+def _filtered_iter(index, batches, k: int, excl: torch.Tensor, excl_off: torch.Tensor, skip: int, ceiling,
+                   to_host: bool, depth):
+    """What FlatIPIndex and ShardedFlatIP share: the index's own search at depth K (filtered_depth), then
+    kernels.topk_exclude on each batch with that batch's view of ``excl_off`` ([b + 1] absolute offsets: the
+    CSR is never re-based) and of ``ceiling``."""
+    batches = list(batches)
+    nq = sum(int(q.shape[0]) for q in batches)
+    if excl_off.numel() != nq + 1:
+        raise ValueError(f"excl_off holds {excl_off.numel()} offsets for {nq} queries (expected nq + 1)")
+    if ceiling is not None and ceiling.numel() != nq:
+        raise ValueError(f"ceiling holds {ceiling.numel()} values for {nq} queries")
+    if not batches:
+        return
+    K = filtered_depth(k, skip, excl_off, index.ntotal, depth)
+    o = 0
+    for s, i in index.search_batches_iter(batches, K):
+        b = s.shape[0]
+        fs, fi, cnt = kernels.topk_exclude(s, i, excl, excl_off[o: o + b + 1], k, skip=skip,
+                                           ceiling=None if ceiling is None else ceiling[o: o + b])
+        o += b
+        yield (fs.cpu().numpy(), fi.cpu().numpy(), cnt.cpu().numpy()) if to_host else (fs, fi, cnt)
+
+
 class _GroupPend:
     """One enqueued group of ``FlatIPIndex.enqueue_batches`` (its result, once finished)."""
     __slots__ = ("pend", "k", "id_offset", "res")
@@ -552,6 +591,39 @@ class FlatIPIndex:
         s, i = self.search_device(q, k)
         return s.cpu().numpy(), i.cpu().numpy()
 
+    # filtered search: top-k of (corpus minus a per-query id set) -- hard-negative mining
+    # (the skip loop of BM25Negatives.load_passages, DRT/trainer/sampler.py:69-80, on the device)
+    def search_filtered_batches_iter(self, batches, k: int, excl, excl_off, *, skip: int = 0, ceiling=None,
+                                     to_host: bool = False, depth: Optional[int] = None):
+        """Exact top-k of every query over the rows NOT in its exclusion segment, optionally scoring below
+        its ``ceiling`` and after its first ``skip`` survivors.  ``excl`` int64 [E] / ``excl_off`` int64
+        [nq + 1]: a CSR over all the batches' queries in order, each segment sorted ascending
+        (trainer.mining.build_exclusions); ``ceiling`` fp32 [nq] or None.  The index is searched at depth
+        K = skip + k + the longest segment (``search_batches_iter``: grouped up to 2048, the large-k path
+        beyond, ValueError past MAX_K_LARGE) and each batch compacted by kernels.topk_exclude: exact,
+        because a query's list loses at most |segment| entries.  ``depth``: search deeper than the rule
+        (with a ceiling the number dropped is unknown: ``count`` tells).  Yields per batch (scores [b, k],
+        ids [b, k], count [b] = the query's survivors in the depth-K list before skip / k); short rows are
+        padded (-FLT_MAX, -1)."""
+        dev = self.device
+        yield from _filtered_iter(self, batches, k, excl.to(dev), excl_off.to(dev), skip,
+                                  None if ceiling is None else ceiling.to(device=dev, dtype=torch.float32), to_host,
+                                  depth)
+
+    def search_filtered_device(self, q, k: int, excl, excl_off, *, skip: int = 0, ceiling=None,
+                               depth: Optional[int] = None):
+        """One batch of ``search_filtered_batches_iter``: (scores [nq, k], ids [nq, k], count [nq])."""
+        return next(self.search_filtered_batches_iter([self._queries(q)], k, excl, excl_off, skip=skip,
+                                                      ceiling=ceiling, depth=depth))
+
+    def pair_scores(self, q, qidx, ids) -> torch.Tensor:
+        """fp32 [npairs]: the score this index's canonical search reports for query ``qidx[j]`` (a row of
+        ``q``) and row ``ids[j]`` (kernels.pair_scores); -FLT_MAX for an id the index does not hold."""
+        dev = self.device
+        qidx = torch.as_tensor(qidx, dtype=torch.int32).to(dev)
+        ids = torch.as_tensor(ids, dtype=torch.int64).to(dev)
+        return kernels.pair_scores(self._queries(q), self.rows, qidx, ids)
+
     # global-threshold protocol steps (ShardedFlatIP) ---------------------
     def _pad(self, x: torch.Tensor) -> torch.Tensor:
         return x if self.dp == self.d else torch.nn.functional.pad(x, (0, self.dp - self.d))
@@ -726,6 +798,32 @@ class ShardedFlatIP:
             if to_host and isinstance(r[0], torch.Tensor):
                 r = (r[0].cpu().numpy(), r[1].cpu().numpy())
             yield r
+
+    def search_filtered_batches_iter(self, batches, k: int, excl, excl_off, *, skip: int = 0, ceiling=None,
+                                     to_host: bool = False, depth: Optional[int] = None):
+        """FlatIPIndex.search_filtered_batches_iter over the sharded search: every rank passes the same
+        batches and the same exclusions (GLOBAL ids); the depth-K lists are already merged and carry global
+        ids, so each rank compacts them alike.  Rejects what ``search_batches_iter`` rejects at depth K."""
+        dev = self.local.device
+        yield from _filtered_iter(self, batches, k, excl.to(dev), excl_off.to(dev), skip,
+                                  None if ceiling is None else ceiling.to(device=dev, dtype=torch.float32), to_host,
+                                  depth)
+
+    def search_filtered_device(self, q, k: int, excl, excl_off, *, skip: int = 0, ceiling=None,
+                               depth: Optional[int] = None):
+        """One batch of ``search_filtered_batches_iter``: (scores [nq, k], ids [nq, k], count [nq])."""
+        return next(self.search_filtered_batches_iter([q], k, excl, excl_off, skip=skip, ceiling=ceiling,
+                                                      depth=depth))
+
+    def pair_scores(self, q, qidx, ids) -> torch.Tensor:
+        """FlatIPIndex.pair_scores for GLOBAL ids (collective): each rank scores the pairs whose rows it
+        owns (-FLT_MAX elsewhere) and a MAX all-reduce completes the answer on every rank."""
+        dev = self.local.device
+        ids = torch.as_tensor(ids, dtype=torch.int64).to(dev)
+        out = self.local.pair_scores(q, qidx, ids - self.offset)
+        if self._multi():
+            comm.all_reduce_max_(out, self.group)
+        return out
 
     def group_chunks(self):
         """This shard's row chunks of a group filter: as many as the largest shard needs (every rank the

@@ -184,6 +184,34 @@ int drt_topk_merge(const float* scores, const int64_t* ids, int64_t nq, int32_t 
                    void* stream);
 
 /* ------------------------------------------------------------------------
+ * Hard-negative mining: top-m of (corpus minus a per-query id set)
+ * ------------------------------------------------------------------------
+ * drt_topk_exclude: the skip loop of BM25Negatives.load_passages (DRT/trainer/sampler.py:69-80: search
+ *   num_negative + len(positives), drop the sample's own positives, keep the first num_negative) as a
+ *   stable compaction of a canonical top-k list on the device.  scores / ids [nq, k_in] are a search
+ *   result (exact score desc, id asc, pads (-FLT_MAX, -1)); entry j of query q is kept iff ids[q][j] >= 0,
+ *   ids[q][j] is not in excl[excl_off[q] .. excl_off[q + 1]) (each segment sorted ascending; duplicates and
+ *   ids absent from the list are harmless; excl_off [nq + 1] holds absolute offsets into excl) and
+ *   (ceiling == NULL or scores[q][j] < ceiling[q]).  Kept entries keep their order; survivors number
+ *   skip .. skip + k_out - 1 go to out_scores / out_ids [nq, k_out], the rest of which is (-FLT_MAX, -1);
+ *   out_count[q] = the number kept, before skip and k_out apply.
+ *   Exactness rule: with E_q the excluded set, the first skip + m survivors of the top-K list are exactly
+ *   the top-(skip + m) of the corpus minus E_q provided K >= skip + m + |E_q| (at most |E_q| entries are
+ *   dropped), so a filtered search is the search at depth K = skip + m + max_q |E_q| plus this pass.  With
+ *   a ceiling the number dropped is not known beforehand: out_count tells which queries came up short.
+ *   1 <= k_in <= 32768, k_out >= 1, skip >= 0.
+ * drt_pair_scores_bf16: out[j] = the fp64 sum of the bf16 products of query qidx[j] (row of Q [nq, d]) and
+ *   row rows[j] of P [n, d], rounded once to fp32 -- the score the canonical stage reports for that pair
+ *   (the positives' scores a positive-aware filter compares with; sampler.py:69-80 has no such step).  A row
+ *   outside [0, n) (or a query outside [0, nq)) gives -FLT_MAX, so each shard answers for the rows it owns
+ *   and a MAX all-reduce completes the answer.  d % 8 == 0, d <= 1024.                                  */
+int drt_topk_exclude(const float* scores, const int64_t* ids, int64_t nq, int32_t k_in, const int64_t* excl,
+                     const int64_t* excl_off, const float* ceiling, int32_t skip, int32_t k_out,
+                     float* out_scores, int64_t* out_ids, int32_t* out_count, void* stream);
+int drt_pair_scores_bf16(const void* Q, int64_t nq, const void* P, int64_t n, int32_t d, const int32_t* qidx,
+                         const int64_t* rows, int64_t npairs, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Distributed exact top-k with ONE global threshold (row shards, one process
  * per GPU).  Replaces the same boundary as drt_ip_topk_bf16 + drt_topk_merge
  * (faiss search per partition + merge_retrieval_results_by_score,
