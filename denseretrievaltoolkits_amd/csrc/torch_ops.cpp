@@ -13,7 +13,7 @@
 //   HF BertModel forward pieces        transformers modeling_bert.py       drt::embed_ln, linear,
 //                                                                          attention, layernorm, pool,
 //                                                                          l2_normalize
-// Fake (meta) kernels and the autograd formula of score_ce_fwd are registered from Python
+// Fake (meta) kernels and the autograd formulas of score_ce_fwd / score_kd_fwd are registered from Python
 // (denseretrievaltoolkits_amd/ops.py).
 #include <vector>
 
@@ -634,6 +634,66 @@ std::tuple<Tensor, Tensor> score_ce_bwd(const Tensor& grad_, const Tensor& q_, c
   return {dq, dp};
 }
 
+// teacher [m, group] next to q [m, d] / p [n, d]; the C entry checks group, temperature and the weights
+static void need_kd(const Tensor& q, const Tensor& p, const Tensor& teacher, int64_t group) {
+  need(q, "q", at::kFloat, 2);
+  need(p, "p", at::kFloat, 2);
+  need(teacher, "teacher", at::kFloat, 2);
+  TORCH_CHECK_VALUE(q.size(1) == p.size(1), "q ", q.sizes(), " and p ", p.sizes(), " differ in dimension");
+  TORCH_CHECK_VALUE(teacher.size(0) == q.size(0) && teacher.size(1) == group, "teacher ", teacher.sizes(),
+                    ": expected [", q.size(0), ", ", group, "]");
+  TORCH_CHECK_VALUE(p.device() == q.device() && teacher.device() == q.device(), "q, p and teacher on one device");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> score_kd_fwd(const Tensor& q_, const Tensor& p_, const Tensor& teacher_,
+                                                        int64_t group, double temperature, double w_ce,
+                                                        double w_kd, double scale) {
+  need_kd(q_, p_, teacher_, group);
+  const c10::DeviceGuard g(q_.device());
+  const Tensor q = q_.contiguous(), p = p_.contiguous(), teacher = teacher_.contiguous();
+  const int64_t m = q.size(0), n = p.size(0), d = q.size(1);
+  Tensor S = at::empty({m, n}, q.options());
+  Tensor lse = at::empty({m}, q.options());
+  Tensor aux = at::empty({m, 2}, q.options());
+  Tensor loss = at::empty({}, q.options());
+  const size_t wsb = drt_score_kd_workspace(m, n, (int32_t)d);
+  Tensor ws = workspace(q, wsb);
+  check_rc(drt_score_kd_fwd(q.data_ptr<float>(), p.data_ptr<float>(), teacher.data_ptr<float>(), m, n, (int32_t)d,
+                            group, (float)temperature, (float)w_ce, (float)w_kd, (float)scale, S.data_ptr<float>(),
+                            lse.data_ptr<float>(), aux.data_ptr<float>(), loss.data_ptr<float>(), ws.data_ptr(), wsb,
+                            stream_of(q)),
+           "drt_score_kd_fwd");
+  return {loss, S, lse, aux};
+}
+
+std::tuple<Tensor, Tensor> score_kd_bwd(const Tensor& grad_, const Tensor& q_, const Tensor& p_,
+                                        const Tensor& teacher_, const Tensor& S_, const Tensor& lse_,
+                                        const Tensor& aux_, int64_t group, double temperature, double w_ce,
+                                        double w_kd, double scale) {
+  need_kd(q_, p_, teacher_, group);
+  need(S_, "scores", at::kFloat, 2);
+  need(lse_, "lse", at::kFloat, 1);
+  need(aux_, "aux", at::kFloat, 2);
+  const int64_t m = q_.size(0), n = p_.size(0), d = q_.size(1);
+  TORCH_CHECK_VALUE(S_.size(0) == m && S_.size(1) == n && lse_.size(0) == m && aux_.size(0) == m && aux_.size(1) == 2,
+                    "scores ", S_.sizes(), ", lse ", lse_.sizes(), ", aux ", aux_.sizes(), ": expected [", m, ", ", n,
+                    "], [", m, "], [", m, ", 2]");
+  const c10::DeviceGuard g(q_.device());
+  const Tensor q = q_.contiguous(), p = p_.contiguous(), teacher = teacher_.contiguous(), S = S_.contiguous(),
+               lse = lse_.contiguous(), aux = aux_.contiguous();
+  const Tensor grad = grad_.to(at::kFloat).contiguous().reshape({1});
+  Tensor dq = at::empty({m, d}, q.options());
+  Tensor dp = at::empty({n, d}, q.options());
+  const size_t wsb = drt_score_kd_workspace(m, n, (int32_t)d);
+  Tensor ws = workspace(q, wsb);
+  check_rc(drt_score_kd_bwd(q.data_ptr<float>(), p.data_ptr<float>(), teacher.data_ptr<float>(), S.data_ptr<float>(),
+                            lse.data_ptr<float>(), aux.data_ptr<float>(), m, n, (int32_t)d, group, (float)temperature,
+                            (float)w_ce, (float)w_kd, grad.data_ptr<float>(), (float)scale, dq.data_ptr<float>(),
+                            dp.data_ptr<float>(), ws.data_ptr(), wsb, stream_of(q)),
+           "drt_score_kd_bwd");
+  return {dq, dp};
+}
+
 // ---------------------------------------------------------------------------- encoder pieces
 Tensor embed_ln(const Tensor& ids_, const c10::optional<Tensor>& type_ids, const Tensor& word, const Tensor& pos,
                 const Tensor& type, const Tensor& gamma, const Tensor& beta, double eps) {
@@ -775,6 +835,10 @@ TORCH_LIBRARY(drt, m) {
   m.def("score_ce_fwd(Tensor q, Tensor p, int target_stride, float scale) -> (Tensor, Tensor, Tensor)");
   m.def("score_ce_bwd(Tensor grad, Tensor q, Tensor p, Tensor scores, Tensor lse, int target_stride, "
         "float scale) -> (Tensor, Tensor)");
+  m.def("score_kd_fwd(Tensor q, Tensor p, Tensor teacher, int group, float temperature, float w_ce, float w_kd, "
+        "float scale) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("score_kd_bwd(Tensor grad, Tensor q, Tensor p, Tensor teacher, Tensor scores, Tensor lse, Tensor aux, "
+        "int group, float temperature, float w_ce, float w_kd, float scale) -> (Tensor, Tensor)");
   m.def("embed_ln(Tensor input_ids, Tensor? token_type_ids, Tensor word, Tensor pos, Tensor type, Tensor gamma, "
         "Tensor beta, float eps) -> Tensor");
   m.def("linear(Tensor x, Tensor w, Tensor? bias, Tensor? residual, bool gelu=False, bool fp32_out=False) -> Tensor");
@@ -809,6 +873,8 @@ TORCH_LIBRARY_IMPL(drt, CUDA, m) {   // the GPU dispatch key of torch-ROCm
   m.impl("pair_scores", &pair_scores);
   m.impl("score_ce_fwd", &score_ce_fwd);
   m.impl("score_ce_bwd", &score_ce_bwd);
+  m.impl("score_kd_fwd", &score_kd_fwd);
+  m.impl("score_kd_bwd", &score_kd_bwd);
   m.impl("embed_ln", &embed_ln);
   m.impl("linear", &linear);
   m.impl("attention", &attention);

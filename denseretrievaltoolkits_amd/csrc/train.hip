@@ -11,7 +11,11 @@
 //   drt_gemm_nt_f32      C = A . B^T                 (fp32 in / out)
 //   drt_ce_fwd           lse_i, mean loss
 //   drt_ce_bwd           dS = (softmax(S) - onehot) * g * scale / m
+//   drt_kd_fwd / _bwd    the same with a KL term towards teacher scores of each query's own passages
+//                        (cross-encoder distillation; no counterpart in the reference)
 //   drt_transpose_f32    helper for the backward GEMMs (dQ = dS P, dP = dS^T Q)
+#include <cmath>
+
 #include "drt_common.h"
 
 namespace drt {
@@ -528,6 +532,159 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* S, const float
   }
 }
 
+// ---- distillation (score_kd): CE over the whole row + KL(teacher || student) over the row's group of g
+// columns [i*g, i*g+g), both at temperature T.  The group pass is strided, so any g works.
+
+// block-wide max / sum of two values at once (256 threads, fixed order); red holds 8 floats
+__device__ __forceinline__ void block_max2(float& a, float& b, float* red) {
+  a = warp_max(a);
+  b = warp_max(b);
+  __syncthreads();   // red may still be read from the previous round
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; red[4 + (threadIdx.x >> 6)] = b; }
+  __syncthreads();
+  a = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  b = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+}
+__device__ __forceinline__ void block_add2(float& a, float& b, float* red) {
+  a = warp_add(a);
+  b = warp_add(b);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; red[4 + (threadIdx.x >> 6)] = b; }
+  __syncthreads();
+  a = red[0] + red[1] + red[2] + red[3];
+  b = red[4] + red[5] + red[6] + red[7];
+}
+
+// Group pass of row i: grp = S + i*n + i*g, tch = teacher + i*g.  Returns KL_i (every thread) and stores
+// aux[i] = (lse of S/T, lse of teacher/T) over the group.  A teacher entry of -inf has probability 0 and adds
+// nothing; a row of them has lse_t = -inf and KL_i = 0.
+// x / T is a true division in every pass, here and in the backward (never x * (1/T), a product the compiler
+// contracts into the subtraction behind it): the same element then has the same bits wherever it is formed, so a
+// group of one column gives exactly softmax = 1 and KL = 0.
+__device__ __forceinline__ float kd_group_pass(const float* grp, const float* tch, int64_t g, float T,
+                                               float* aux_i, float* red) {
+  const float ninf = -__builtin_inff();
+  float ms = ninf, mt = ninf;
+  for (int64_t j = threadIdx.x; j < g; j += 256) {
+    ms = fmaxf(ms, grp[j] / T);
+    mt = fmaxf(mt, tch[j] / T);
+  }
+  block_max2(ms, mt, red);
+  const bool dropped = mt == ninf;   // uniform over the block
+  float ss = 0.f, st = 0.f;
+  for (int64_t j = threadIdx.x; j < g; j += 256) {
+    ss += expf(grp[j] / T - ms);
+    if (!dropped) st += expf(tch[j] / T - mt);
+  }
+  block_add2(ss, st, red);
+  const float ls = ms + logf(ss);
+  const float lt = dropped ? ninf : mt + logf(st);
+  if (threadIdx.x == 0) { aux_i[0] = ls; aux_i[1] = lt; }
+  float kl = 0.f, unused = 0.f;
+  if (!dropped)
+    for (int64_t j = threadIdx.x; j < g; j += 256) {
+      const float t = tch[j] / T;
+      if (t != ninf) {
+        const float lpt = t - lt;
+        kl += expf(lpt) * (lpt - (grp[j] / T - ls));
+      }
+    }
+  block_add2(kl, unused, red);
+  return kl;
+}
+
+// ce_fwd_kernel + the group pass: row_loss_i = w_ce * CE_i + w_kd * KL_i
+__global__ __launch_bounds__(256) void kd_fwd_kernel(const float* S, const float* teacher, int64_t m, int64_t n,
+                                                     int64_t g, float T, float w_ce, float w_kd, float* lse,
+                                                     float* aux, float* row_loss) {
+  __shared__ float red[8];
+  const int64_t i = blockIdx.x;
+  const float* row = S + i * n;
+  float mx = -__builtin_inff();
+  for (int64_t j = threadIdx.x; j < n; j += 256) mx = fmaxf(mx, row[j]);
+  mx = warp_max(mx);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float sum = 0.f;
+  for (int64_t j = threadIdx.x; j < n; j += 256) sum += expf(row[j] - mx);
+  sum = warp_add(sum);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  const float l = mx + logf(red[0] + red[1] + red[2] + red[3]);
+  const float kl = kd_group_pass(row + i * g, teacher + i * g, g, T, aux + 2 * i, red);
+  if (threadIdx.x == 0) {
+    lse[i] = l;
+    const float ce = l - row[i * g];
+    row_loss[i] = w_ce * ce + w_kd * kl;
+  }
+}
+
+// ce_fwd_reduce_kernel + the group pass.  The group columns of S are written in the row pass by other threads
+// of this work-group, so the group pass reads them only after the work-group barriers of the row reductions
+// (__syncthreads orders global writes at work-group scope; one work-group runs on one CU and shares its L1).
+__global__ __launch_bounds__(256) void kd_fwd_reduce_kernel(const float* ws, int64_t z, float* S,
+                                                            const float* teacher, int64_t m, int64_t n, int64_t g,
+                                                            float T, float w_ce, float w_kd, float* lse,
+                                                            float* aux, float* row_loss) {
+  __shared__ float red[8];
+  const int64_t i = blockIdx.x;
+  float* row = S + i * n;
+  const int64_t e = m * n;
+  float mx = -__builtin_inff();
+  for (int64_t j = threadIdx.x; j < n; j += 256) {
+    float v = ws[i * n + j];
+    for (int64_t u = 1; u < z; ++u) v += ws[u * e + i * n + j];
+    row[j] = v;
+    mx = fmaxf(mx, v);
+  }
+  mx = warp_max(mx);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float sum = 0.f;
+  for (int64_t j = threadIdx.x; j < n; j += 256) sum += expf(row[j] - mx);   // own writes: same thread
+  sum = warp_add(sum);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();   // also orders every thread's row[] writes before the group pass below
+  const float l = mx + logf(red[0] + red[1] + red[2] + red[3]);
+  const float* grp = row + i * g;
+  const float kl = kd_group_pass(grp, teacher + i * g, g, T, aux + 2 * i, red);
+  if (threadIdx.x == 0) {
+    lse[i] = l;
+    const float ce = l - grp[0];
+    row_loss[i] = w_ce * ce + w_kd * kl;
+  }
+}
+
+// dS_ij = coef * (w_ce * (softmax(S_i)_j - [j == i*g]) + [j in group] * w_kd / T * (softmax(s_i) - softmax(t_i))),
+// one store per element.  A dropped row (lse_t = -inf) has no distillation term.
+__global__ __launch_bounds__(256) void kd_bwd_kernel(const float* S, const float* teacher, const float* lse,
+                                                     const float* aux, int64_t m, int64_t n, int64_t g,
+                                                     float T, float w_ce, float w_kd, const float* grad,
+                                                     float scale, float* dS) {
+  const int64_t i = blockIdx.x;
+  const float coef = (grad ? *grad : 1.0f) * scale / (float)m;
+  const float l = lse[i];
+  const float ls = aux[2 * i], lt = aux[2 * i + 1];
+  const int64_t t = i * g;
+  const float ninf = -__builtin_inff();
+  const float wk = lt == ninf ? 0.f : w_kd / T;
+  for (int64_t j = threadIdx.x; j < n; j += 256) {
+    const float v = S[i * n + j];
+    const float p = expf(v - l);
+    float kd = 0.f;
+    if (j >= t && j < t + g && wk != 0.f) {
+      const float tv = teacher[j] / T;   // teacher[i*g + (j - t)], and t = i*g
+      const float pt = tv == ninf ? 0.f : expf(tv - lt);
+      kd = wk * (expf(v / T - ls) - pt);
+    }
+    dS[i * n + j] = coef * (w_ce * (p - (j == t ? 1.0f : 0.0f)) + kd);
+  }
+}
+
 __global__ __launch_bounds__(256) void transpose_f32_kernel(const float* X, int64_t rows, int64_t cols, float* Y) {
   __shared__ float t[32][33];
   const int64_t r0 = (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
@@ -686,14 +843,17 @@ size_t drt_score_ce_workspace(int64_t m, int64_t n, int32_t d) {
   return score_ce_ws_floats(m, n, d, nullptr, nullptr) * sizeof(float);
 }
 
-// S = q . p^T (exact f32), lse, loss = scale * mean_i (lse_i - S[i][i * target_stride]).
-// 3 launches: GEMM (split-K partials or S itself) -> per-row (split reduce + LSE + row loss) ->
-// fixed-order mean.
-int drt_score_ce_fwd(const float* q, const float* p, int64_t m, int64_t n, int32_t d, int64_t target_stride,
-                     float scale, float* S, float* lse, float* loss, void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(m > 0 && n > 0 && d > 0 && target_stride >= 0 && (m - 1) * target_stride < n);
-  DRT_REQUIRE(q && p && S && lse && loss && ws && ws_bytes >= drt_score_ce_workspace(m, n, d));
-  hipStream_t s = (hipStream_t)stream;
+// GEMM half of the fused forwards (CE and KD share it): S = q . p^T or its split-K partials, one launch.
+// z partials of m * n floats lie at ws when reduce is set (the row kernel then sums them into S); row_loss
+// is the m floats of workspace behind them.
+struct ScoreFwd {
+  const float* part;
+  int64_t z;
+  bool reduce;
+  float* row_loss;
+};
+static ScoreFwd launch_score_fwd_gemm(const float* q, const float* p, int64_t m, int64_t n, int32_t d, float* S,
+                                      void* ws, hipStream_t s) {
   int64_t kc, z;
   float* part = (float*)ws;
   if (large_f32_ok(q, p, m, n, d)) {
@@ -703,14 +863,7 @@ int drt_score_ce_fwd(const float* q, const float* p, int64_t m, int64_t n, int32
               (int)cdiv(m, 128), (int)cdiv(n, kFwdTN), (int)z, 1};
     const int64_t blocks = (int64_t)g.tiles_m * g.tiles_n * z;
     hipLaunchKernelGGL(score_fwd_gemm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
-    if (z > 1)
-      hipLaunchKernelGGL(ce_fwd_reduce_kernel, dim3((unsigned)m), dim3(256), 0, s, (const float*)part, z, S, m, n,
-                         target_stride, lse, row_loss);
-    else
-      hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)m), dim3(256), 0, s, (const float*)S, m, n, target_stride,
-                         lse, row_loss);
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, m, scale, loss);
-    return hip_status(hipGetLastError());
+    return {part, z, z > 1, row_loss};
   }
   split_plan(m, n, d, kc, z);
   float* row_loss = part + (size_t)z * m * n;
@@ -720,20 +873,13 @@ int drt_score_ce_fwd(const float* q, const float* p, int64_t m, int64_t n, int32
                               (int64_t)d, (int64_t)d, (int64_t)d, n, kc);
   else hipLaunchKernelGGL((gemm_f32_kernel<true, true, false>), grid, dim3(256), 0, s, q, p, part, m, n,
                           (int64_t)d, (int64_t)d, (int64_t)d, n, kc);
-  hipLaunchKernelGGL(ce_fwd_reduce_kernel, dim3((unsigned)m), dim3(256), 0, s, (const float*)part, z, S, m, n,
-                     target_stride, lse, row_loss);
-  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, m, scale, loss);
-  return hip_status(hipGetLastError());
+  return {part, z, true, row_loss};
 }
 
-// dS = scale * g / m * (softmax(S) - onehot); dq = dS . p; dp = dS^T . q.
-// 3 launches: dS -> both GEMMs in one grid (split-K partials) -> both fixed-order reductions.
-int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float* lse, int64_t m, int64_t n,
-                     int32_t d, int64_t target_stride, const float* grad, float scale, float* dq, float* dp,
-                     void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(m > 0 && n > 0 && d > 0 && target_stride >= 0 && (m - 1) * target_stride < n);
-  DRT_REQUIRE(q && p && S && lse && dq && dp && ws && ws_bytes >= drt_score_ce_workspace(m, n, d));
-  hipStream_t s = (hipStream_t)stream;
+// GEMM half of the fused backwards: dq = dS . p and dp = dS^T . q from the dS [m][n] at the head of ws
+// (2 launches: both GEMMs in one grid, both fixed-order split reductions).
+static void launch_score_bwd_gemms(const float* q, const float* p, int64_t m, int64_t n, int32_t d, float* dq,
+                                   float* dp, void* ws, hipStream_t s) {
   float* dS = (float*)ws;
   int64_t kc0, z0, kc1, z1;
   if (large_f32_ok(q, p, m, n, d)) {
@@ -746,8 +892,6 @@ int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float
     F32Prob g1{dS, q, z1 > 1 ? ws1 : dp, n, (int64_t)d, m, n, (int64_t)d, (int64_t)d, kc1,
                (int)cdiv(n, 128), tn, (int)z1, 0};
     const int64_t nb0 = (int64_t)g0.tiles_m * tn * z0, nb1 = (int64_t)g1.tiles_m * tn * z1;
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)m), dim3(256), 0, s, S, lse, m, n, target_stride, grad, scale,
-                       dS);
     hipLaunchKernelGGL(score_bwd_gemm_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, s, g0, g1, nb0);
     const int64_t e0 = z0 > 1 ? m * d : 0, e1 = z1 > 1 ? n * d : 0;
     if (e0 + e1 > 0) {
@@ -755,7 +899,7 @@ int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float
       hipLaunchKernelGGL(dual_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, s, (const float*)ws0, z0, e0, dq,
                          (const float*)ws1, z1, e1, dp);
     }
-    return hip_status(hipGetLastError());
+    return;
   }
   DualGemm g{};
   split_plan(m, d, n, kc0, z0);
@@ -766,7 +910,6 @@ int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float
   g.m = m; g.n = n; g.d = d;
   g.kchunk0 = kc0; g.kchunk1 = kc1; g.z0 = z0; g.z1 = z1;
   g.tn = (d + kGT - 1) / kGT;
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)m), dim3(256), 0, s, S, lse, m, n, target_stride, grad, scale, dS);
   const int64_t blocks = ((m + kGT - 1) / kGT) * g.tn * z0 + ((n + kGT - 1) / kGT) * g.tn * z1;
   const bool vec = ((uintptr_t)q % 16 == 0) && ((uintptr_t)p % 16 == 0) && d % 4 == 0 && n % 4 == 0;
   if (vec) hipLaunchKernelGGL(gemm_f32_dual_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, g);
@@ -775,6 +918,103 @@ int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float
   const int64_t rb = (e0 + e1 + 255) / 256 < 2048 ? (e0 + e1 + 255) / 256 : 2048;
   hipLaunchKernelGGL(dual_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, s, (const float*)g.ws0, z0, e0, dq,
                      (const float*)g.ws1, z1, e1, dp);
+}
+
+// S = q . p^T (exact f32), lse, loss = scale * mean_i (lse_i - S[i][i * target_stride]).
+// 3 launches: GEMM (split-K partials or S itself) -> per-row (split reduce + LSE + row loss) ->
+// fixed-order mean.
+int drt_score_ce_fwd(const float* q, const float* p, int64_t m, int64_t n, int32_t d, int64_t target_stride,
+                     float scale, float* S, float* lse, float* loss, void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(m > 0 && n > 0 && d > 0 && target_stride >= 0 && (m - 1) * target_stride < n);
+  DRT_REQUIRE(q && p && S && lse && loss && ws && ws_bytes >= drt_score_ce_workspace(m, n, d));
+  hipStream_t s = (hipStream_t)stream;
+  const ScoreFwd f = launch_score_fwd_gemm(q, p, m, n, d, S, ws, s);
+  if (f.reduce)
+    hipLaunchKernelGGL(ce_fwd_reduce_kernel, dim3((unsigned)m), dim3(256), 0, s, f.part, f.z, S, m, n,
+                       target_stride, lse, f.row_loss);
+  else
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)m), dim3(256), 0, s, (const float*)S, m, n, target_stride,
+                       lse, f.row_loss);
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float*)f.row_loss, m, scale, loss);
+  return hip_status(hipGetLastError());
+}
+
+// dS = scale * g / m * (softmax(S) - onehot); dq = dS . p; dp = dS^T . q.
+// 3 launches: dS -> both GEMMs in one grid (split-K partials) -> both fixed-order reductions.
+int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float* lse, int64_t m, int64_t n,
+                     int32_t d, int64_t target_stride, const float* grad, float scale, float* dq, float* dp,
+                     void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(m > 0 && n > 0 && d > 0 && target_stride >= 0 && (m - 1) * target_stride < n);
+  DRT_REQUIRE(q && p && S && lse && dq && dp && ws && ws_bytes >= drt_score_ce_workspace(m, n, d));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)m), dim3(256), 0, s, S, lse, m, n, target_stride, grad, scale,
+                     (float*)ws);
+  launch_score_bwd_gemms(q, p, m, n, d, dq, dp, ws, s);
+  return hip_status(hipGetLastError());
+}
+
+// ---- distillation: loss = scale * mean_i (w_ce * CE_i + w_kd * KL_i), see drt.h.  Query i owns columns
+// [i*g, i*g+g) of S and row i of teacher [m][g]; aux [m][2] = (lse of S_group / T, lse of teacher / T).
+static bool kd_args_ok(int64_t m, int64_t n, int64_t g, float temperature, float w_ce, float w_kd) {
+  return m > 0 && n > 0 && g >= 1 && g <= n && m <= n / g && temperature > 0.f && std::isfinite(temperature) &&
+         w_ce >= 0.f && w_kd >= 0.f;
+}
+
+int drt_kd_fwd(const float* S, const float* teacher, int64_t m, int64_t n, int64_t group, float temperature,
+               float w_ce, float w_kd, float scale, float* lse, float* aux, float* row_loss, float* loss,
+               void* stream) {
+  DRT_REQUIRE(kd_args_ok(m, n, group, temperature, w_ce, w_kd));
+  DRT_REQUIRE(S && teacher && lse && aux && row_loss && loss);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kd_fwd_kernel, dim3((unsigned)m), dim3(256), 0, s, S, teacher, m, n, group,
+                     temperature, w_ce, w_kd, lse, aux, row_loss);
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, m, scale, loss);
+  return hip_status(hipGetLastError());
+}
+
+int drt_kd_bwd(const float* S, const float* teacher, const float* lse, const float* aux, int64_t m, int64_t n,
+               int64_t group, float temperature, float w_ce, float w_kd, const float* grad, float scale,
+               float* dS, void* stream) {
+  DRT_REQUIRE(kd_args_ok(m, n, group, temperature, w_ce, w_kd));
+  DRT_REQUIRE(S && teacher && lse && aux && dS);
+  hipLaunchKernelGGL(kd_bwd_kernel, dim3((unsigned)m), dim3(256), 0, (hipStream_t)stream, S, teacher, lse, aux, m,
+                     n, group, temperature, w_ce, w_kd, grad, scale, dS);
+  return hip_status(hipGetLastError());
+}
+
+// the CE workspace serves both: same GEMM plans, and aux is an output
+size_t drt_score_kd_workspace(int64_t m, int64_t n, int32_t d) { return drt_score_ce_workspace(m, n, d); }
+
+// 3 launches, as drt_score_ce_fwd with the KD row kernels
+int drt_score_kd_fwd(const float* q, const float* p, const float* teacher, int64_t m, int64_t n, int32_t d,
+                     int64_t group, float temperature, float w_ce, float w_kd, float scale, float* S, float* lse,
+                     float* aux, float* loss, void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(d > 0 && kd_args_ok(m, n, group, temperature, w_ce, w_kd));
+  DRT_REQUIRE(q && p && teacher && S && lse && aux && loss && ws && ws_bytes >= drt_score_kd_workspace(m, n, d));
+  hipStream_t s = (hipStream_t)stream;
+  const ScoreFwd f = launch_score_fwd_gemm(q, p, m, n, d, S, ws, s);
+  if (f.reduce)
+    hipLaunchKernelGGL(kd_fwd_reduce_kernel, dim3((unsigned)m), dim3(256), 0, s, f.part, f.z, S, teacher, m, n,
+                       group, temperature, w_ce, w_kd, lse, aux, f.row_loss);
+  else
+    hipLaunchKernelGGL(kd_fwd_kernel, dim3((unsigned)m), dim3(256), 0, s, (const float*)S, teacher, m, n, group,
+                       temperature, w_ce, w_kd, lse, aux, f.row_loss);
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float*)f.row_loss, m, scale, loss);
+  return hip_status(hipGetLastError());
+}
+
+// 3 launches, as drt_score_ce_bwd with kd_bwd_kernel
+int drt_score_kd_bwd(const float* q, const float* p, const float* teacher, const float* S, const float* lse,
+                     const float* aux, int64_t m, int64_t n, int32_t d, int64_t group, float temperature,
+                     float w_ce, float w_kd, const float* grad, float scale, float* dq, float* dp, void* ws,
+                     size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(d > 0 && kd_args_ok(m, n, group, temperature, w_ce, w_kd));
+  DRT_REQUIRE(q && p && teacher && S && lse && aux && dq && dp && ws &&
+              ws_bytes >= drt_score_kd_workspace(m, n, d));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kd_bwd_kernel, dim3((unsigned)m), dim3(256), 0, s, S, teacher, lse, aux, m, n, group,
+                     temperature, w_ce, w_kd, grad, scale, (float*)ws);
+  launch_score_bwd_gemms(q, p, m, n, d, dq, dp, ws, s);
   return hip_status(hipGetLastError());
 }
 

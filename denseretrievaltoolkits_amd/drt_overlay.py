@@ -27,6 +27,8 @@ HOT_PATH_MODULES = {
     # dense hard-negative mining (no counterpart file in the reference: DenseNegatives stands beside
     # BM25Negatives of DRT/trainer/sampler.py, which keeps resolving to the user's package)
     "DRT.trainer.mining": "denseretrievaltoolkits_amd.trainer.mining",
+    # cross-encoder distillation (no counterpart file either: DistillTrainer stands beside Trainer)
+    "DRT.trainer.distill": "denseretrievaltoolkits_amd.trainer.distill",
 }
 
 

@@ -15,7 +15,8 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   HIP kernels, HF train-mode dropout regenerated from a counter hash; dropout is
   off in eval mode); other towers stay on the HF module under autograd.
 * the training score matrix + cross entropy (forward :107-119) runs on the
-  fused fp32 kernels with autograd (torch.ops.drt.score_ce_fwd, score_ce.py).
+  fused fp32 kernels with autograd (torch.ops.drt.score_ce_fwd, score_ce.py); with
+  ``forward(..., teacher_scores=)`` the distillation loss of torch.ops.drt.score_kd_fwd.
 """
 from __future__ import annotations
 
@@ -106,7 +107,8 @@ class DRModel(nn.Module):
         }
 
     # ------------------------------------------------------------------
-    def forward(self, query: Dict[str, Tensor] = None, passage: Dict[str, Tensor] = None):
+    def forward(self, query: Dict[str, Tensor] = None, passage: Dict[str, Tensor] = None,
+                teacher_scores: Optional[Tensor] = None):
         q_hidden, q_reps = self.encode_query(query)
         p_hidden, p_reps = self.encode_passage(passage)
         if query is None or passage is None:
@@ -115,17 +117,30 @@ class DRModel(nn.Module):
         if x_dev:
             q_reps = self.dist_gather_tensor(q_reps)
             p_reps = self.dist_gather_tensor(p_reps)
+            if teacher_scores is not None:
+                teacher_scores = self.dist_gather_tensor(teacher_scores.detach())
         n_passages = self.data_args.train_n_passages
         scale = float(self.world_size) if (self.training and x_dev) else 1.0
-        from ..score_ce import score_ce
+        from ..score_ce import score_ce, score_kd
+        if teacher_scores is None:
+            def score(q, p, t):
+                return score_ce(q, p, n_passages, scale)
+        else:
+            # distillation towards a cross-encoder's scores [B, n_passages] (trainer/distill.py)
+            kd = dict(temperature=float(getattr(self.train_args, "distill_temperature", 1.0)),
+                      w_ce=float(getattr(self.train_args, "distill_ce_weight", 0.0)),
+                      w_kd=float(getattr(self.train_args, "distill_kd_weight", 1.0)), scale=scale)
+
+            def score(q, p, t):
+                return score_kd(q, p, t.to(q.device), n_passages, **kd)
         if q_reps.is_cuda:
-            loss, scores = score_ce(q_reps, p_reps, n_passages, scale)
+            loss, scores = score(q_reps, p_reps, teacher_scores)
         elif torch.cuda.is_available():
             # a tower on the CPU (the reference scores on any device, biencoder.py:107-116): the reps go to
             # the GPU for the fused HIP op and the loss / scores come back; autograd carries the gradients
             # across both copies to the CPU tower
             dev = torch.device("cuda", torch.cuda.current_device())
-            loss, scores = score_ce(q_reps.to(dev), p_reps.to(dev), n_passages, scale)
+            loss, scores = score(q_reps.to(dev), p_reps.to(dev), teacher_scores)
             loss, scores = loss.to(q_reps.device), scores.to(q_reps.device)
         else:
             raise ValueError("DRModel.forward: the MI355X build computes the score matrix on the GPU only "

@@ -4,7 +4,7 @@ The operators are defined in C++ (csrc/torch_ops.cpp, ``TORCH_LIBRARY(drt, ...)`
 ``_drt_ops.so`` next to ``libdrt_hip.so``) over the C ABI of ``include/drt.h``.  This module
 loads that library (no fallback: a missing library raises) and registers, per operator, the
 fake (meta) implementation that torch.compile / FakeTensor tracing need, plus the autograd
-formula of the fused score + cross-entropy op.
+formulas of the fused score + cross-entropy and score + distillation ops.
 
     torch.ops.drt.ip_topk(q, p, k, id_offset, stats)   -> (scores, ids, status)   index.py:31-33
     torch.ops.drt.ip_topk_resolve(q, p, k, off, s, i, st, stats) -> n_resolved  (in place, synchronous)
@@ -18,6 +18,9 @@ formula of the fused score + cross-entropy op.
     torch.ops.drt.pair_scores(q, p, qidx, rows)         -> scores                  sampler.py:69-80 (mining)
     torch.ops.drt.score_ce_fwd(q, p, stride, scale)     -> (loss, scores, lse)     biencoder.py:107-119
     torch.ops.drt.score_ce_bwd(g, q, p, scores, lse, stride, scale) -> (dq, dp)
+    torch.ops.drt.score_kd_fwd(q, p, teacher, group, T, w_ce, w_kd, scale) -> (loss, scores, lse, aux)
+    torch.ops.drt.score_kd_bwd(g, q, p, teacher, scores, lse, aux, group, T, w_ce, w_kd, scale) -> (dq, dp)
+                                                        (distillation: CE + KL to teacher scores, score_ce.score_kd)
     torch.ops.drt.embed_ln / linear / attention / layernorm / pool / l2_normalize  (BertModel pieces)
 """
 from __future__ import annotations
@@ -168,6 +171,15 @@ def _register_python_parts():
     def _(grad, q, p, scores, lse, target_stride, scale):
         return q.new_empty(q.shape), p.new_empty(p.shape)
 
+    @lib.register_fake("drt::score_kd_fwd")
+    def _(q, p, teacher, group, temperature, w_ce, w_kd, scale):
+        m = q.shape[0]
+        return q.new_empty(()), q.new_empty((m, p.shape[0])), q.new_empty((m,)), q.new_empty((m, 2))
+
+    @lib.register_fake("drt::score_kd_bwd")
+    def _(grad, q, p, teacher, scores, lse, aux, group, temperature, w_ce, w_kd, scale):
+        return q.new_empty(q.shape), p.new_empty(p.shape)
+
     @lib.register_fake("drt::embed_ln")
     def _(input_ids, token_type_ids, word, pos, type, gamma, beta, eps):
         return input_ids.new_empty(tuple(input_ids.shape) + (word.shape[1],), dtype=torch.bfloat16)
@@ -208,3 +220,18 @@ def _register_python_parts():
         return dq, dp, None, None
 
     lib.register_autograd("drt::score_ce_fwd", backward, setup_context=setup_context)
+
+    # the distillation loss likewise: the loss is differentiable in q and p only (the teacher is a target)
+    def kd_setup_context(ctx, inputs, output):
+        q, p, teacher, group, temperature, w_ce, w_kd, scale = inputs
+        _, scores, lse, aux = output
+        ctx.save_for_backward(q, p, teacher, scores, lse, aux)
+        ctx.kd_args = (int(group), float(temperature), float(w_ce), float(w_kd), float(scale))
+        ctx.mark_non_differentiable(scores, lse, aux)
+
+    def kd_backward(ctx, g_loss, g_scores, g_lse, g_aux):
+        q, p, teacher, scores, lse, aux = ctx.saved_tensors
+        dq, dp = torch.ops.drt.score_kd_bwd(g_loss, q, p, teacher, scores, lse, aux, *ctx.kd_args)
+        return dq, dp, None, None, None, None, None, None
+
+    lib.register_autograd("drt::score_kd_fwd", kd_backward, setup_context=kd_setup_context)

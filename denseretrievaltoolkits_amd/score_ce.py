@@ -65,3 +65,25 @@ def score_ce(q: torch.Tensor, p: torch.Tensor, target_stride: int, scale: float 
         raise ValueError(f"q {tuple(q.shape)} and p {tuple(p.shape)} differ in dimension")
     loss, scores, _ = ops.load().score_ce_fwd(q.float(), p.float(), int(target_stride), float(scale))
     return loss, scores
+
+
+def score_kd(q: torch.Tensor, p: torch.Tensor, teacher: torch.Tensor, group: int, *, temperature: float = 1.0,
+             w_ce: float = 0.0, w_kd: float = 1.0, scale: float = 1.0):
+    """(loss, scores) of the distillation loss: query i owns passages [i * group, i * group + group)
+    (positive first) and row i of ``teacher`` [m, group], e.g. a cross-encoder's scores of them.
+
+        loss = scale * mean_i (w_ce * CE_i + w_kd * KL(softmax(teacher_i / T) || softmax(S_i,group / T)))
+
+    with CE_i over all n columns as ``score_ce`` (target_stride = group); no implicit T^2 (pass
+    w_kd = T^2 for it).  A teacher entry of -inf drops that passage from the KL, a row of -inf drops
+    the query.  ``torch.ops.drt.score_kd_fwd`` runs score_ce's GEMMs with its own row kernels (3
+    launches per direction); the teacher gets no gradient.  bf16 inputs are promoted to fp32."""
+    if not (q.is_cuda and p.is_cuda and teacher.is_cuda):
+        raise ValueError("score_kd runs on the GPU only (no CPU fallback)")
+    if q.dim() != 2 or p.dim() != 2 or q.shape[1] != p.shape[1]:
+        raise ValueError(f"q {tuple(q.shape)} and p {tuple(p.shape)} differ in dimension")
+    if teacher.dim() != 2 or tuple(teacher.shape) != (q.shape[0], int(group)):
+        raise ValueError(f"teacher {tuple(teacher.shape)}: expected ({q.shape[0]}, {int(group)})")
+    loss, scores, _, _ = ops.load().score_kd_fwd(q.float(), p.float(), teacher.detach().float(), int(group),
+                                                  float(temperature), float(w_ce), float(w_kd), float(scale))
+    return loss, scores

@@ -8,7 +8,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from ..score_ce import score_ce
+from ..score_ce import score_ce, score_kd
 
 
 class SimpleContrastiveLoss(nn.Module):
@@ -42,6 +42,34 @@ class DistributedContrastiveLoss(SimpleContrastiveLoss):
         gathered = comm.all_gather_list(t.contiguous())
         gathered[self.rank] = t
         return torch.cat(gathered, dim=0)
+
+
+class DistillContrastiveLoss(nn.Module):
+    """w_ce * in-batch CE + w_kd * KL(teacher || student) over each query's own passages, at ``temperature``
+    (score_ce.score_kd); ``teacher`` is [queries, passages per query], e.g. a cross-encoder's scores."""
+
+    def __init__(self, temperature: float = 1.0, w_ce: float = 0.0, w_kd: float = 1.0):
+        super().__init__()
+        self.temperature, self.w_ce, self.w_kd = float(temperature), float(w_ce), float(w_kd)
+
+    def forward(self, x: Tensor, y: Tensor, teacher: Tensor):
+        loss, _ = score_kd(x, y, teacher, y.size(0) // x.size(0), temperature=self.temperature, w_ce=self.w_ce,
+                           w_kd=self.w_kd)
+        return loss
+
+
+class DistributedDistillContrastiveLoss(DistillContrastiveLoss):
+    def __init__(self, temperature: float = 1.0, w_ce: float = 0.0, w_kd: float = 1.0, scale_loss: bool = True):
+        assert dist.is_initialized(), "Distributed training has not been properly initialized."
+        super().__init__(temperature, w_ce, w_kd)
+        self.word_size = dist.get_world_size()
+        self.rank = dist.get_rank()
+        self.scale_loss = scale_loss
+
+    def forward(self, x: Tensor, y: Tensor, teacher: Tensor):
+        gather = DistributedContrastiveLoss.gather_tensor
+        loss = super().forward(gather(self, x), gather(self, y), gather(self, teacher.detach()))
+        return loss * self.word_size if self.scale_loss else loss
 
 
 def get_loss_function(training_args):

@@ -540,6 +540,38 @@ int drt_score_ce_fwd(const float* q, const float* p, int64_t m, int64_t n, int32
 int drt_score_ce_bwd(const float* q, const float* p, const float* S, const float* lse, int64_t m, int64_t n,
                      int32_t d, int64_t target_stride, const float* grad, float scale, float* dq, float* dp,
                      void* ws, size_t ws_bytes, void* stream);
+/* Distillation: the same score matrix with a soft-target term (score_ce.score_kd).
+ * Query i owns the `group` columns [i*group, i*group + group) of S (m * group <= n) and
+ * row i of teacher [m, group]; its positive is column i*group.  With s = S_group / T and
+ * t = teacher / T:
+ *   CE_i = lse_j(S_ij) - S[i][i*group]                      (all n columns)
+ *   KL_i = sum_j softmax(t_i)_j (log softmax(t_i)_j - log softmax(s_i)_j)
+ *   *loss = scale * mean_i (w_ce * CE_i + w_kd * KL_i)      (no implicit T^2)
+ *   dS_ij = grad * scale / m * (w_ce * (softmax(S_i)_j - [j == i*group])
+ *           + [j in group] * w_kd / T * (softmax(s_i) - softmax(t_i))_(j - i*group))
+ * A teacher entry of -inf has probability 0 and adds nothing to KL_i (the student's softmax
+ * still spans the whole group); a row of -inf has KL_i = 0 and no distillation term in dS.
+ * +inf or NaN in teacher is the caller's error.  aux [m][2] = (lse of s_i, lse of t_i)
+ * goes from the forward to the backward.  Requires group >= 1, m * group <= n, T > 0 and
+ * finite, w_ce >= 0, w_kd >= 0 (DRT_EINVAL otherwise, before any launch).
+ * drt_kd_fwd / drt_kd_bwd work on a given S like drt_ce_fwd / drt_ce_bwd; the fused
+ * drt_score_kd_fwd / _bwd run the GEMMs of drt_score_ce_fwd / _bwd around them (3 launches
+ * per direction, no host synchronisation, fixed summation order) and need ws of
+ * drt_score_kd_workspace(m, n, d) bytes.  w_ce = 1, w_kd = 0 gives drt_score_ce's bits.  */
+int drt_kd_fwd(const float* S, const float* teacher, int64_t m, int64_t n, int64_t group, float temperature,
+               float w_ce, float w_kd, float scale, float* lse, float* aux, float* row_loss, float* loss,
+               void* stream);
+int drt_kd_bwd(const float* S, const float* teacher, const float* lse, const float* aux, int64_t m, int64_t n,
+               int64_t group, float temperature, float w_ce, float w_kd, const float* grad, float scale,
+               float* dS, void* stream);
+size_t drt_score_kd_workspace(int64_t m, int64_t n, int32_t d);
+int drt_score_kd_fwd(const float* q, const float* p, const float* teacher, int64_t m, int64_t n, int32_t d,
+                     int64_t group, float temperature, float w_ce, float w_kd, float scale, float* S, float* lse,
+                     float* aux, float* loss, void* ws, size_t ws_bytes, void* stream);
+int drt_score_kd_bwd(const float* q, const float* p, const float* teacher, const float* S, const float* lse,
+                     const float* aux, int64_t m, int64_t n, int32_t d, int64_t group, float temperature,
+                     float w_ce, float w_kd, const float* grad, float scale, float* dq, float* dp, void* ws,
+                     size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Launch timing (measurement support for bench.py's roofline figure).
