@@ -9,6 +9,7 @@
 //   per-partition merge                DRT/model/utils.py:215-229          drt::topk_merge, merge_packed
 //   corpus sharding (file exchange)    DRT/trainer/trainer.py:191-262      drt::dist_sample/_tau/_filter
 //   hard-negative skip loop            DRT/trainer/sampler.py:69-80        drt::topk_exclude, pair_scores
+//   document-level (MaxP) dedup        (host-side in the common toolkits)  drt::topk_collapse
 //   score matrix + CE (+ autograd)     DRT/model/biencoder.py:107-119      drt::score_ce_fwd/_bwd
 //   HF BertModel forward pieces        transformers modeling_bert.py       drt::embed_ln, linear,
 //                                                                          attention, layernorm, pool,
@@ -592,6 +593,42 @@ Tensor pair_scores(const Tensor& q_, const Tensor& p_, const Tensor& qidx_, cons
   return out;
 }
 
+// ---------------------------------------------------------------------------- grouped (MaxP) search
+// Stable compaction of a canonical top-k list [nq, k_in] to the first entry of every group (drt_topk_collapse):
+// groups [n_rows] int32 maps a row id to its group; pads and ids outside the map are dropped; the first k_out
+// first occurrences -> (scores, groups int32, ids) [nq, k_out] padded (-FLT_MAX, -1, -1), count [nq] = the
+// first occurrences of the whole list.
+std::tuple<Tensor, Tensor, Tensor, Tensor> topk_collapse(const Tensor& scores_, const Tensor& ids_,
+                                                         const Tensor& groups_, int64_t k_out) {
+  need(scores_, "scores", at::kFloat, 2);
+  need(ids_, "ids", at::kLong, 2);
+  need(groups_, "groups", at::kInt, 1);
+  TORCH_CHECK_VALUE(scores_.sizes() == ids_.sizes(), "topk_collapse: scores ", scores_.sizes(), " and ids ",
+                    ids_.sizes(), " differ in shape");
+  TORCH_CHECK_VALUE(ids_.device() == scores_.device() && groups_.device() == scores_.device(),
+                    "topk_collapse: every tensor must be on the scores' device ", scores_.device());
+  const int64_t nq = scores_.size(0), k_in = scores_.size(1);
+  TORCH_CHECK_VALUE(k_out >= 1 && k_out <= 0x7FFFFFFF, "topk_collapse: unsupported k_out=", k_out, " (k_out >= 1)");
+  TORCH_CHECK_VALUE(k_in >= 1 && k_in <= 32768, "topk_collapse: unsupported list length k_in=", k_in,
+                    " (1 <= k_in <= 32768)");
+  const c10::DeviceGuard g(scores_.device());
+  const Tensor scores = scores_.contiguous(), ids = ids_.contiguous(), groups = groups_.contiguous();
+  Tensor os = at::empty({nq, k_out}, scores.options());
+  Tensor og = at::empty({nq, k_out}, groups.options());
+  Tensor oi = at::empty({nq, k_out}, ids.options());
+  Tensor cnt = at::empty({nq}, scores.options().dtype(at::kInt));
+  if (nq == 0) return {os, og, oi, cnt};
+  const size_t wsb = drt_topk_collapse_workspace(nq, (int32_t)k_in);
+  TORCH_CHECK_VALUE(wsb > 0, "unsupported topk_collapse shape nq=", nq, " k_in=", k_in);
+  Tensor ws = workspace(scores, wsb);
+  check_rc(drt_topk_collapse(scores.data_ptr<float>(), ids.data_ptr<int64_t>(), nq, (int32_t)k_in,
+                             groups.numel() ? groups.data_ptr<int32_t>() : nullptr, groups.numel(), (int32_t)k_out,
+                             os.data_ptr<float>(), og.data_ptr<int32_t>(), oi.data_ptr<int64_t>(),
+                             cnt.data_ptr<int32_t>(), ws.data_ptr(), wsb, stream_of(scores)),
+           "drt_topk_collapse");
+  return {os, og, oi, cnt};
+}
+
 // ---------------------------------------------------------------------------- training loss
 std::tuple<Tensor, Tensor, Tensor> score_ce_fwd(const Tensor& q_, const Tensor& p_, int64_t target_stride,
                                                 double scale) {
@@ -832,6 +869,7 @@ TORCH_LIBRARY(drt, m) {
   m.def("topk_exclude(Tensor scores, Tensor ids, Tensor excl, Tensor excl_off, Tensor? ceiling, int skip, int k_out) -> "
         "(Tensor, Tensor, Tensor)");
   m.def("pair_scores(Tensor q, Tensor p, Tensor qidx, Tensor rows) -> Tensor");
+  m.def("topk_collapse(Tensor scores, Tensor ids, Tensor groups, int k_out) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("score_ce_fwd(Tensor q, Tensor p, int target_stride, float scale) -> (Tensor, Tensor, Tensor)");
   m.def("score_ce_bwd(Tensor grad, Tensor q, Tensor p, Tensor scores, Tensor lse, int target_stride, "
         "float scale) -> (Tensor, Tensor)");
@@ -871,6 +909,7 @@ TORCH_LIBRARY_IMPL(drt, CUDA, m) {   // the GPU dispatch key of torch-ROCm
   m.impl("merge_packed", &merge_packed);
   m.impl("topk_exclude", &topk_exclude);
   m.impl("pair_scores", &pair_scores);
+  m.impl("topk_collapse", &topk_collapse);
   m.impl("score_ce_fwd", &score_ce_fwd);
   m.impl("score_ce_bwd", &score_ce_bwd);
   m.impl("score_kd_fwd", &score_kd_fwd);

@@ -37,6 +37,7 @@ class BaseFaissIPRetriever:
         self.index = index
         self.docid: List = []
         self.last_scores: Optional[np.ndarray] = None
+        self.last_rows: Optional[np.ndarray] = None   # best-row ids of the last grouped search
 
     def add(self, p_reps) -> None:
         self.index.add(p_reps)
@@ -76,6 +77,35 @@ class BaseFaissIPRetriever:
         res = list(self.index.search_batches_iter([qd[a: a + batch_size] for a in range(0, n, batch_size)], k,
                                                   to_host=True))
         self.last_scores = np.concatenate([r[0] for r in res])
+        return np.concatenate([r[1] for r in res])
+
+    # document-level (MaxP) retrieval: rows are passages, groups the documents they were cut from
+    def set_groups(self, groups) -> None:
+        """``groups[row]`` = the group (document) id of every indexed row (FlatIPIndex.set_groups)."""
+        self.index.set_groups(groups)
+
+    def search_grouped(self, q_reps, k: int = 1000, groups=None) -> np.ndarray:
+        """Group ids [nq, k] of the best k groups, each scored by its best row, exactly
+        (FlatIPIndex.search_grouped_batches_iter: no over-fetch guess, no host-side dedup); rows short of k
+        groups are padded -1.  ``last_scores`` / ``last_rows`` keep the best rows' scores and ids.
+        ``groups``: a row -> group map to set first (None: the one ``set_groups`` stored)."""
+        return self.batch_search_grouped(q_reps, k, max(1, q_reps.shape[0]), groups=groups)
+
+    def batch_search_grouped(self, q_reps, k: int, batch_size: int, groups=None) -> np.ndarray:
+        """``search_grouped`` in query batches of ``batch_size`` (batch j + 1 is searched while batch j is
+        collapsed and copied to the host)."""
+        if groups is not None:
+            self.index.set_groups(groups)
+        n = q_reps.shape[0]
+        if n == 0:
+            self.last_scores = np.zeros((0, k), dtype=np.float32)
+            self.last_rows = np.zeros((0, k), dtype=np.int64)
+            return np.zeros((0, k), dtype=np.int32)
+        qd = self.index._queries(q_reps)
+        res = list(self.index.search_grouped_batches_iter([qd[a: a + batch_size] for a in range(0, n, batch_size)], k,
+                                                          to_host=True))
+        self.last_scores = np.concatenate([r[0] for r in res])
+        self.last_rows = np.concatenate([r[2] for r in res])
         return np.concatenate([r[1] for r in res])
 
 

@@ -452,6 +452,42 @@ def pair_scores(q: torch.Tensor, p: torch.Tensor, qidx: torch.Tensor, rows: torc
     return ops.load().pair_scores(q, p, qidx.to(torch.int32), rows.to(torch.int64))
 
 
+COLLAPSE_LDS_K = 2048      # longest list whose group table stays in LDS (csrc/collapse.hip kCollapseLdsK)
+COLLAPSE_LDS_GROUPS = 1024  # work-groups of the LDS form (kCollLdsGroups): more queries reuse their tables
+COLLAPSE_REGIONS = 128     # work-groups = table regions of the workspace form (kCollRegions)
+
+
+def grouped_depths(k: int, p_max: int, ntotal: int) -> Tuple[int, Optional[int]]:
+    """Depth plan (d1, d2) of a grouped search for the best k groups when the largest group holds ``p_max``
+    rows: ``full = min(k * p_max, ntotal)`` always shows k groups or every group there is (the j-th group's
+    best row is preceded only by rows of the j - 1 earlier groups).  d1 = min(full, MAX_K) is the first rung
+    (the candidate-list kernels, the grouped path); d2 = min(full, MAX_K_LARGE) the second, searched only for
+    the queries whose depth-d1 list showed fewer than k groups, or None when d1 is already ``full``.  A query
+    still short at d2 < full has no certified answer (the caller raises)."""
+    if k < 1 or p_max < 1 or ntotal < 0:
+        raise ValueError(f"grouped search needs k >= 1, p_max >= 1, ntotal >= 0 (k={k}, p_max={p_max}, "
+                         f"ntotal={ntotal})")
+    full = max(1, min(k * p_max, int(ntotal)))
+    d1 = max(1, min(full, MAX_K))
+    d2 = max(1, min(full, MAX_K_LARGE)) if full > d1 else None
+    return d1, d2
+
+
+def topk_collapse(scores: torch.Tensor, ids: torch.Tensor, groups: torch.Tensor,
+                  k_out: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Stable compaction of canonical top-k lists [nq, k_in] (k_in <= 32768) to the FIRST entry of every group:
+    ``groups`` int32 [n_rows] maps a row id to its group (0 <= group < 2^31); pads and ids outside
+    [0, n_rows) are dropped.  Returns the first ``k_out`` first occurrences in their input order -- (scores
+    fp32, groups int32, ids int64) [nq, k_out] padded (-FLT_MAX, -1, -1) -- and count int32 [nq] = the first
+    occurrences of the whole list.  The list being in (exact score desc, id asc) order, a group's first entry
+    is its best row and the output is the head of the grouped (MaxP) result; it is the exact top-k_out of the
+    groups whenever count >= k_out or the list is the whole corpus (include/drt.h)."""
+    _require_device(scores, ids, groups)
+    if scores.dim() != 2 or scores.shape != ids.shape:
+        raise ValueError("topk_collapse expects [nq, k_in] scores and ids")
+    return ops.load().topk_collapse(scores, ids, groups, k_out)
+
+
 def gemm_nt_f32(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C = a @ b.T with bf16 inputs and fp32 accumulation/output (MFMA)."""
     lib = _native.load()

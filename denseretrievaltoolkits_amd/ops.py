@@ -16,6 +16,7 @@ formulas of the fused score + cross-entropy and score + distillation ops.
     torch.ops.drt.filter_passes_into   (one GPU's group filter: interleaved passes, tightened threshold)
     torch.ops.drt.topk_exclude(scores, ids, excl, excl_off, ceiling, skip, k_out) -> (scores, ids, count)
     torch.ops.drt.pair_scores(q, p, qidx, rows)         -> scores                  sampler.py:69-80 (mining)
+    torch.ops.drt.topk_collapse(scores, ids, groups, k_out) -> (scores, groups, ids, count)   (grouped / MaxP search)
     torch.ops.drt.score_ce_fwd(q, p, stride, scale)     -> (loss, scores, lse)     biencoder.py:107-119
     torch.ops.drt.score_ce_bwd(g, q, p, scores, lse, stride, scale) -> (dq, dp)
     torch.ops.drt.score_kd_fwd(q, p, teacher, group, T, w_ce, w_kd, scale) -> (loss, scores, lse, aux)
@@ -162,6 +163,12 @@ def _register_python_parts():
     @lib.register_fake("drt::pair_scores")
     def _(q, p, qidx, rows):
         return q.new_empty((rows.shape[0],), dtype=torch.float32)
+
+    @lib.register_fake("drt::topk_collapse")
+    def _(scores, ids, groups, k_out):
+        nq = scores.shape[0]
+        return (scores.new_empty((nq, k_out), dtype=torch.float32), groups.new_empty((nq, k_out), dtype=torch.int32),
+                ids.new_empty((nq, k_out), dtype=torch.int64), scores.new_empty((nq,), dtype=torch.int32))
 
     @lib.register_fake("drt::score_ce_fwd")
     def _(q, p, target_stride, scale):

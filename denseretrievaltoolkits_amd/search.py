@@ -353,6 +353,60 @@ def _filtered_iter(index, batches, k: int, excl: torch.Tensor, excl_off: torch.T
         yield (fs.cpu().numpy(), fi.cpu().numpy(), cnt.cpu().numpy()) if to_host else (fs, fi, cnt)
 
 
+def prepare_groups(groups, device) -> Tuple[torch.Tensor, int]:
+    """(int32 [n] device tensor, P_max) of a row -> group map: 1-d, integer, 0 <= group < 2^31 (ValueError
+    otherwise).  P_max = the largest group's row count -- the max of the bincount of the groups relabelled
+    densely (a bincount of the raw ids would allocate up to 2^31 bins); 1 for an empty map.  Synchronises."""
+    g = groups if isinstance(groups, torch.Tensor) else torch.as_tensor(np.asarray(groups))
+    if g.dim() != 1 or g.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"groups must be a 1-d integer array (got {tuple(g.shape)} {g.dtype})")
+    g = g.to(device)
+    if g.numel():
+        lo, hi = int(g.min().item()), int(g.max().item())
+        if lo < 0 or hi >= 2 ** 31:
+            raise ValueError(f"group ids must lie in [0, 2^31) (got {lo} .. {hi})")
+    g = g.to(torch.int32).contiguous()
+    p_max = int(torch.unique(g, return_counts=True)[1].max().item()) if g.numel() else 1
+    return g, p_max
+
+
+def _grouped_iter(index, prep, batches, k: int, groups: Optional[torch.Tensor], p_max: int, to_host: bool):
+    """What FlatIPIndex and ShardedFlatIP share (DESIGN.md "Grouped search"): per batch the index's own search
+    at depth d1 and kernels.topk_collapse; the queries whose list showed fewer than k groups (one read-back of
+    ``count`` per batch) are searched again, only they and once, at depth d2 and scattered back
+    (kernels.grouped_depths).  A list that shows k groups, holds a pad or is ``full`` deep is exact by the
+    prefix property; a query still short at d2 < full raises -- no uncertified grouped result is returned.
+    ``prep``: the index's query preparation (a device tensor to gather the short queries from)."""
+    batches = list(batches)
+    if groups is None:
+        raise ValueError("grouped search needs a row -> group map: call set_groups first")
+    if groups.numel() != index.ntotal:
+        raise ValueError(f"groups maps {groups.numel()} rows, the index holds {index.ntotal} (set_groups again "
+                         "after adding rows)")
+    d1, d2 = kernels.grouped_depths(k, p_max, index.ntotal)
+    full = max(1, min(k * p_max, int(index.ntotal)))
+    batches = [prep(q) for q in batches]
+    for q, (s, i) in zip(batches, index.search_batches_iter(batches, d1)):
+        gs, gg, gi, cnt = kernels.topk_collapse(s, i, groups, k)
+        if d2 is not None:
+            # (pads fill a canonical list's tail, so its last id tells whether it held one)
+            short = torch.nonzero((cnt < k) & (i[:, -1] >= 0)).flatten()
+            if short.numel():
+                s2, i2 = next(iter(index.search_batches_iter([q.index_select(0, short).contiguous()], d2)))
+                gs2, gg2, gi2, cnt2 = kernels.topk_collapse(s2, i2, groups, k)
+                if d2 < full:
+                    still = int(((cnt2 < k) & (i2[:, -1] >= 0)).sum().item())
+                    if still:
+                        raise ValueError(f"grouped search: {still} queries show fewer than k={k} groups in their top "
+                                         f"{d2} rows (MAX_K_LARGE); an exact answer would need depth {full} = "
+                                         f"min(k * P_max, ntotal) with P_max={p_max}")
+                gs.index_copy_(0, short, gs2)
+                gg.index_copy_(0, short, gg2)
+                gi.index_copy_(0, short, gi2)
+                cnt.index_copy_(0, short, cnt2)
+        yield tuple(t.cpu().numpy() for t in (gs, gg, gi, cnt)) if to_host else (gs, gg, gi, cnt)
+
+
 class _GroupPend:
     """One enqueued group of ``FlatIPIndex.enqueue_batches`` (its result, once finished)."""
     __slots__ = ("pend", "k", "id_offset", "res")
@@ -389,6 +443,8 @@ class FlatIPIndex:
         self.exact_order = EXACT_ORDER
         self._stats = None     # row statistics of rows [0, _stats_n) (kernels.row_stats)
         self._stats_n = 0
+        self._groups = None    # row -> group map of the grouped search (set_groups), int32 on the device
+        self._p_max = 1        # its largest group's row count
 
     # faiss-compatible surface -----------------------------------------
     @property
@@ -399,6 +455,8 @@ class FlatIPIndex:
         self.ntotal = 0
         self._stats = None   # refilled rows must be rescanned (a stale max-norm / integer flag would
         self._stats_n = 0    # make the canonical stage's error bound wrong)
+        self._groups = None  # (the row -> group map described the rows that are gone)
+        self._p_max = 1
 
     def reserve(self, n: int):
         if n > self._buf.shape[0]:
@@ -616,6 +674,31 @@ class FlatIPIndex:
         return next(self.search_filtered_batches_iter([self._queries(q)], k, excl, excl_off, skip=skip,
                                                       ceiling=ceiling, depth=depth))
 
+    # grouped search: the best k GROUPS (documents), each scored by its best row (passage) -- MaxP
+    def set_groups(self, groups) -> None:
+        """``groups``: a 1-d integer array mapping every row to its group id (0 <= id < 2^31), kept on the
+        device as int32 with P_max, the largest group's row count (prepare_groups).  It must cover the rows
+        the index holds when it is searched: set it again after ``add``; ``reset`` clears it."""
+        self._groups, self._p_max = prepare_groups(groups, self.device)
+
+    def search_grouped_batches_iter(self, batches, k: int, *, to_host: bool = False):
+        """Exact top-k groups of every query: the groups ordered by the canonical position (exact score desc,
+        row id asc) of their best rows.  Yields per batch (scores fp32 [b, k] = the best rows' scores, group
+        ids int32 [b, k], row ids int64 [b, k] = the best rows, count int32 [b] = the groups the deepest list
+        searched for the query showed); short rows are padded (-FLT_MAX, -1, -1).  The index is searched at
+        depth min(k * P_max, ntotal, 2048) and each batch collapsed by kernels.topk_collapse; the queries
+        whose list showed fewer than k groups are searched once more at min(k * P_max, ntotal, 32768), and
+        ValueError says how many are still short there (_grouped_iter)."""
+        yield from _grouped_iter(self, self._queries, batches, k, self._groups, self._p_max, to_host)
+
+    def search_grouped_device(self, q, k: int):
+        """One batch of ``search_grouped_batches_iter``: (scores, group ids, row ids, count) on the device."""
+        return next(self.search_grouped_batches_iter([q], k))
+
+    def search_grouped(self, q, k: int):
+        """``search_grouped_device`` as numpy arrays."""
+        return tuple(t.cpu().numpy() for t in self.search_grouped_device(q, k))
+
     def pair_scores(self, q, qidx, ids) -> torch.Tensor:
         """fp32 [npairs]: the score this index's canonical search reports for query ``qidx[j]`` (a row of
         ``q``) and row ``ids[j]`` (kernels.pair_scores); -FLT_MAX for an id the index does not hold."""
@@ -707,6 +790,8 @@ class ShardedFlatIP:
         self.offset = 0      # global id of this shard's first row
         self.ntotal = 0      # rows over all shards
         self.stats = None    # GLOBAL row statistics (max over shards), set by sync_offsets
+        self._groups = None  # GLOBAL row -> group map of the grouped search (set_groups)
+        self._p_max = 1
         # grouped search: run each group's exchange + merge + canonical stage on a side stream and a
         # second communicator, beside the next group's scans (_SideChannel).  Off by default: the
         # group's filter launch keeps one 153-KiB-LDS, 512-VGPR work-group on EVERY CU for its whole
@@ -814,6 +899,25 @@ class ShardedFlatIP:
         """One batch of ``search_filtered_batches_iter``: (scores [nq, k], ids [nq, k], count [nq])."""
         return next(self.search_filtered_batches_iter([q], k, excl, excl_off, skip=skip, ceiling=ceiling,
                                                       depth=depth))
+
+    def set_groups(self, groups) -> None:
+        """FlatIPIndex.set_groups for the GLOBAL rows: every rank passes the same map of all ``ntotal`` rows
+        (the merged lists carry global ids, so each rank collapses them alike)."""
+        self._groups, self._p_max = prepare_groups(groups, self.local.device)
+
+    def search_grouped_batches_iter(self, batches, k: int, *, to_host: bool = False):
+        """FlatIPIndex.search_grouped_batches_iter over the sharded search: every rank passes the same batches.
+        Rejects what ``search_batches_iter`` rejects at either depth; one rank delegates fully to its shard."""
+        yield from _grouped_iter(self, getattr(self.local, "_queries", lambda q: q), batches, k, self._groups,
+                                 self._p_max, to_host)
+
+    def search_grouped_device(self, q, k: int):
+        """One batch of ``search_grouped_batches_iter``: (scores, group ids, row ids, count) on the device."""
+        return next(self.search_grouped_batches_iter([q], k))
+
+    def search_grouped(self, q, k: int):
+        """``search_grouped_device`` as numpy arrays."""
+        return tuple(t.cpu().numpy() for t in self.search_grouped_device(q, k))
 
     def pair_scores(self, q, qidx, ids) -> torch.Tensor:
         """FlatIPIndex.pair_scores for GLOBAL ids (collective): each rank scores the pairs whose rows it

@@ -212,6 +212,36 @@ int drt_pair_scores_bf16(const void* Q, int64_t nq, const void* P, int64_t n, in
                          const int64_t* rows, int64_t npairs, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Grouped (document-level, MaxP) search: the best k groups, each scored by its best row
+ * ------------------------------------------------------------------------
+ * Definitions.  groups [n_rows] int32 maps each row to a group id (its document), 0 <= group < 2^31.  A
+ *   group's BEST ROW is its first row in the canonical row order (exact score desc, row id asc).  The grouped
+ *   result of a query is the groups ordered by the canonical position of their best rows, cut at k; each hit
+ *   reports the best row's score (the exact fp64 sum rounded once to fp32, as the search reports it), the
+ *   group id and the best row's id; short results are padded (-FLT_MAX, -1, -1).
+ * drt_topk_collapse: scores / ids [nq, k_in] are a search result (canonical order, pads (-FLT_MAX, -1)).
+ *   Entry j of query q is a FIRST OCCURRENCE iff 0 <= ids[q][j] < n_rows and no earlier entry of the query has
+ *   the same groups[id]; pads and ids outside [0, n_rows) are dropped.  First occurrences keep their input
+ *   order; the first k_out go to out_scores (fp32) / out_groups (int32) / out_ids (int64) [nq, k_out], the
+ *   rest of which is (-FLT_MAX, -1, -1); out_count[q] = the first occurrences of the whole list, before the
+ *   cut at k_out.  The result does not depend on the order the entries are processed in.
+ *   Exactness rule: (1) prefix property -- a group's best row precedes all its other rows and groups are
+ *   ordered by best row, so for ANY depth D the first-occurrence groups of the canonical top-D list, in list
+ *   order, are exactly the first groups of the grouped result: a depth-D list that shows >= k groups gives the
+ *   exact top-k groups, and a list that holds pads or has D >= ntotal is the whole corpus, exact whatever it
+ *   shows.  (2) depth bound -- with P_max the largest group's row count, the j-th group's best row is preceded
+ *   only by rows of the j - 1 earlier groups, so depth min(k * P_max, ntotal) always shows k groups or every
+ *   group the corpus has.  A grouped search is the search at such a depth plus this pass.
+ *   1 <= k_in <= 32768, k_out >= 1.  workspace: drt_topk_collapse_workspace(nq, k_in) bytes (> 0 for a
+ *   supported shape, 0 for a rejected one; bounded whatever nq: a fixed number of work-groups loop over the
+ *   queries, each owning one table region; lists of k_in <= 2048 keep their table in LDS and read no
+ *   workspace), 8-byte aligned.  No allocation, no synchronisation.                                      */
+size_t drt_topk_collapse_workspace(int64_t nq, int32_t k_in);
+int drt_topk_collapse(const float* scores, const int64_t* ids, int64_t nq, int32_t k_in, const int32_t* groups,
+                      int64_t n_rows, int32_t k_out, float* out_scores, int32_t* out_groups, int64_t* out_ids,
+                      int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Distributed exact top-k with ONE global threshold (row shards, one process
  * per GPU).  Replaces the same boundary as drt_ip_topk_bf16 + drt_topk_merge
  * (faiss search per partition + merge_retrieval_results_by_score,
