@@ -798,9 +798,27 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
 // tile is loaded by half as many work-groups).  Registers: the 32 queries' fragments (2 x d/32 x 4
 // VGPRs) leave room for a short fragment roll only: fragment s + RD of the same tile (or, near the
 // end of a tile, of the next one) is read into the register fragment s just left, so a slot is read
-// during its own tile and is refilled one tile later (issue distance NB - 1).  A tile's epilogue runs
-// after the next tile's MFMAs are issued (two accumulator sets alternate), as in ip_scan16r.
+// during its own tile (and, its first RD fragments, at the end of the tile before).  A tile's epilogue
+// runs after the next tile's MFMAs are issued (two accumulator sets alternate), as in ip_scan16r.
 // Every score is the same 24-step 16x16x32 chain as ip_scan16r's: identical values and hits.
+// Ring protocol: ONE wait + work-group barrier per PAIR of tiles (it, it+1), it even; slot of tile t is
+// t mod 6; the tile at loop index j refills slot(j-2) with tile j+4, a quarter into its MFMAs.
+//   At the pair's barrier a wave has issued tiles .. it+3 and lets one tile (it+3) stay outstanding
+//   (vmcnt), so its shares of it+1 and it+2 have landed (it+2: the last RD k-steps of it+1 read its
+//   first fragments; tile it was certified by the pair before).  The barrier certifies
+//     RAW: every wave's share of tiles it+1 and it+2 has landed;
+//     WAR: every wave has issued all MFMAs of tiles it-2 and it-1, hence finished reading those slots
+//          (each MFMA waited for its own fragment) -- they are refilled with it+4 (during tile it) and
+//          it+5 (during it+1).  Both refills are legal from the barrier on; one per tile keeps the
+//          issue spread as it was with a barrier per tile.
+//   No barrier between the two tiles of a pair: waves drift by up to two tiles, so their hit checks,
+//   append paths and DMA issue fall out of phase and one wave's append no longer holds up the other
+//   seven at every tile.
+//   Slot census during a pair: it-2, it-1 refilling (tiles it+4, it+5); it, it+1 being read; it+2
+//   landed; it+3 in flight = 6.  A tile is issued >= 2 tile times before the barrier that needs it.
+//   Prologue: tiles 0 .. 3 issued, 0 .. 2 waited for, barrier (= pair 0's).  Every wave of a block runs
+//   1 + (my_tiles - 1) / 2 barriers (my_tiles is block-uniform); no DMA is issued for a tile index >=
+//   my_tiles (do_dma); near the end of a block the wait is for everything outstanding.
 // ---------------------------------------------------------------------------
 template <int D>
 struct Scan32Cfg {
@@ -809,6 +827,8 @@ struct Scan32Cfg {
   static constexpr int TILE_BYTES = kT16 * D * 2;
   static constexpr int HIT_BYTES = kHitCap * 9;
   static constexpr int NB_RAW = (160 * 1024 - HIT_BYTES) / TILE_BYTES;
+  // 6 slots (what fits at d = 768), all accounted for by the pair protocol above: 2 refilling, 2 being
+  // read, 1 landed, 1 in flight
   static constexpr int NB = NB_RAW > 6 ? 6 : NB_RAW;
   static constexpr int RING_BYTES = NB * TILE_BYTES;
   static constexpr int LDS_BYTES = RING_BYTES + HIT_BYTES;
@@ -823,7 +843,8 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   using C = Scan16Cfg<D, NW>;   // tile image, DMA split, per-wave issue count
   using C32 = Scan32Cfg<D>;
   constexpr int NB = C32::NB;
-  constexpr int PD = NB - 1;    // tiles issued ahead (the slot of tile it-1 is refilled at tile it+1)
+  constexpr int PD = NB - 2;    // tiles issued ahead (tile it refills the slot of tile it-2 with tile it+PD)
+  static_assert(NB == 6, "the pair protocol's slot census");
   constexpr int KS = C32::KS;
   constexpr int RD = C32::RD;
   constexpr int kSeg = kHitCap / NW;
@@ -895,10 +916,9 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
     }
   }
   if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-  {
-    const int last = my_tiles - 1 < PD - 1 ? my_tiles - 1 : PD - 1;
-    wait_tiles_younger<C::GLDS_PER_WAVE>((int)last);
-  }
+  // tiles 0 .. 2 landed (tile 3 may stay outstanding): this is also the first pair's barrier
+  if (PD <= my_tiles) wait_vmcnt<C::GLDS_PER_WAVE>();
+  else wait_vmcnt<0>();
   lds_barrier();
 
   const int sw = (r >> 1) & 7;
@@ -943,28 +963,32 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   };
 
   int buf = 0;   // slot of tile it
-  // one tile: wait + barrier, ring refill, MFMAs (+ the rolled reads), then the epilogue of the
-  // PREVIOUS tile (its accumulators are complete by then: no wait on this tile's MFMA latency); the
-  // loop body runs two tiles so the accumulator sets alternate without run-time selection
+  // the pair's one synchronisation point, before its first (even) tile `it`.  Issued so far: tiles
+  // .. it+3.  This wave's shares of tiles it+1 and it+2 must have landed (one tile, it+3, may stay
+  // outstanding; near the end of the block nothing younger than it+2 was issued: wait for all).  After
+  // the barrier every wave's share of them has landed, and every wave has issued the MFMAs of tiles
+  // it-2 and it-1 (so its reads of those two slots completed: each MFMA waited for its own fragment)
+  // -- the two slots the pair refills
+  auto pair_sync = [&](int it) {
+    if (it + PD <= my_tiles) wait_vmcnt<C::GLDS_PER_WAVE>();
+    else wait_vmcnt<0>();
+    lds_barrier();
+  };
+  // one tile: ring refill, MFMAs (+ the rolled reads), then the epilogue of the PREVIOUS tile (its
+  // accumulators are complete by then: no wait on this tile's MFMA latency); the loop body runs the
+  // two tiles of a pair so the accumulator sets alternate without run-time selection
   auto iter = [&](int it, f32x4& acc0, f32x4& acc1, uint32_t& rb, const f32x4& prev0, const f32x4& prev1,
                   uint32_t rb_prev) {
     const int tile = t0 + it * tstep;
-    // issued so far: tiles .. it + PD - 1; tile it+1 must have landed (its first RD fragments are
-    // read near the end of this tile's MFMAs)
-    if (it + PD <= my_tiles) {
-      wait_vmcnt<C::GLDS_PER_WAVE * (PD - 2)>();
-    } else if (it + 1 < my_tiles) {
-      wait_tiles_younger<C::GLDS_PER_WAVE>(my_tiles - 1 - it - 1);
-    }
-    // every wave's share of tile it+1 landed, and every wave issued tile it-1's MFMAs (so its reads of
-    // slot(it-1) completed: each MFMA waited for its own fragment) -- that slot is refilled below
-    lds_barrier();
-    // the refill of slot(it-1) is issued a quarter into this tile's MFMAs (its SALU / address work then
-    // overlaps queued matrix work instead of delaying every wave's first MFMA after the barrier: round 5,
-    // 2.89-2.91 vs 2.95-2.97 ms per grouped launch in three alternating rounds, profiles/r05y)
+    // the refill of slot(it-2) with tile it+PD is issued a quarter into this tile's MFMAs (its SALU /
+    // address work then overlaps queued matrix work instead of delaying every wave's first MFMA after
+    // the barrier: round 5, 2.89-2.91 vs 2.95-2.97 ms per grouped launch in three alternating rounds,
+    // profiles/r05y).  Counted from the pair's first tile e, that tile refills slot(e-2) and the
+    // second one slot(e-1): both free since the pair's barrier; one refill per tile keeps the issue
+    // spread (both in the first tile measured slower, profiles/r11a)
     const bool do_dma = it + PD < my_tiles;
     const int ntile = tile + PD * tstep;
-    const int pslot = buf == 0 ? NB - 1 : buf - 1;   // slot of tile it-1 (it = 0: the unused slot)
+    const int pslot = buf < 2 ? buf + NB - 2 : buf - 2;   // slot of tile it-2 (it < 2: a slot not yet used)
     const int nslot = buf + 1 == NB ? 0 : buf + 1;
     acc0 = (f32x4){0.f, 0.f, 0.f, 0.f};
     acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -989,6 +1013,7 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   f32x4 a0, a1, b0, b1;
   uint32_t rbA = 0, rbB = 0;
   for (int it = 0; it < my_tiles; it += 2) {
+    if (it > 0) pair_sync(it);   // (the prologue's barrier is pair 0's)
     iter(it, a0, a1, rbA, b0, b1, rbB);
     if (it + 1 < my_tiles) iter(it + 1, b0, b1, rbB, a0, a1, rbA);
   }
