@@ -240,7 +240,8 @@ struct AttnArgs {
 // unrolled, O leaves through LDS as whole-row 16-B stores); NB = 0: any L <= 512 (inference), a
 // wave loops over its query blocks and stores directly.
 // Round 3: scores in log2 units, s2 = fma(s, log2e, kb) with the key bias kb = 0 / -FLT_MAX (finite:
-// a row with every key masked gets HF's uniform softmax, no NaN); the running max moves only when a
+// a row with every key masked gets HF's uniform softmax over its L keys, no NaN; the padding keys
+// L..Lp-1 get -inf, which key 0's finite score keeps out of any inf - inf); the running max moves only when a
 // tile's max exceeds it by more than kLazy (= 8, P <= 2^8 in bf16 / fp32 is exact to the same
 // relative precision), so the O rescale is a rare wave-uniform branch instead of 32 multiplies per
 // tile; dropout draws the keep decisions from the pairwise hash (drt_common.h), zeroes dropped P,
@@ -326,7 +327,7 @@ void attention_fwd_kernel(AttnArgs a) {
   }
   for (int i = tid; i < Lp; i += NT) {
     float bv = 0.0f;
-    if (i >= L) bv = -3.402823466e+38f;
+    if (i >= L) bv = -__builtin_inff();   // tile padding: P exactly 0, in a row of masked keys too
     else if (a.mask && a.mask[b * a.L + i] == 0) bv = -3.402823466e+38f;  // (1 - mask) * finfo.min
     kb[i] = bv;
   }
