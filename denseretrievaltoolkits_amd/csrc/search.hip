@@ -317,6 +317,71 @@ struct LeanTile {
   }
 };
 
+// Loader-half issue for ip_scan32r: FOUR waves (one per SIMD, lw = wave & 3) issue a whole tile, G =
+// GLDS_PER_TILE / 4 pieces each (6 at d = 768); called from those waves only.  Piece j of loader wave lw
+// is wave-instruction J = 4 j + lw of the tile image: chunk group 2 j + (lw >> 1), row half lw & 1, so a
+// lane's source offset for piece j is its offset for piece 0 plus j x 256 B and the LDS destination moves
+// by 4 KiB: ONE voff VGPR, the instruction's immediate offset (<= 1,280) and one s_add per piece.  The
+// immediate offset of an LDS-DMA load is added to the global AND the LDS address, so piece j's m0 is the
+// slot's piece-0 address + j x (4,096 - 256).  Same bytes to the same LDS addresses as LeanTile<D, 8> /
+// issue_tile16.  A short last tile takes the same statement with the lane's row clamped to the shard's
+// last row (the source only: the LDS position keeps the lane's own row, as in issue_tile16), so every
+// tile is G pieces for its loader wave.
+// Widths whose piece count is not a multiple of four (d = 64, 192, 320, ...) are not issued this way.
+template <int D>
+struct HalfTile {
+  using C = Scan16Cfg<D, 4>;
+  static constexpr bool kOk = C::GLDS_PER_TILE % 4 == 0 && C::GLDS_PER_TILE <= 24;
+  static constexpr int G = C::GLDS_PER_TILE / 4;
+  uint32_t voff;   // per lane: byte offset of its 16-B chunk of piece 0 from the tile's first row
+  uint32_t loff;   // wave-uniform: LDS byte offset of piece 0 within a slot
+  __device__ __forceinline__ void init(const ScanArgs& a, int wave, int lane) {
+    const int lw = wave & 3;
+    const int row = ((lw & 1) << 3) + (lane >> 3);
+    const int c = (lane & 7) ^ ((row >> 1) & 7);
+    voff = (uint32_t)((row * a.ldp + (lw >> 1) * 64 + c * 8) * 2);
+    loff = (uint32_t)__builtin_amdgcn_readfirstlane(lw * 1024);
+  }
+  // `base` = the tile's first row; `partial` = the shard's last tile and it is short; `tile` = its index
+  // in the shard
+  __device__ __forceinline__ void issue(const ScanArgs& a, uint32_t slot_lds, const char* base, bool partial,
+                                        int tile, int wave, int lane) {
+    static_assert(kOk, "loader half: a multiple of four pieces per tile");
+    uint32_t v = voff;
+    if (partial) {
+      const int row = ((wave & 1) << 3) + (lane >> 3);
+      const int last = (int)(a.nrows - 1 - (int64_t)tile * kT16);   // 0 .. 14
+      if (row > last) v -= (uint32_t)((row - last) * a.ldp * 2);
+    }
+    const uint32_t l0 = slot_lds + loff;
+    uint32_t keep;
+#define DRT_HALF_PIECE(LDS, OFF) \
+  "s_add_u32 m0, %2, " #LDS "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1 offset:" #OFF "\n\t"
+#define DRT_HALF_ISSUE(PIECES) \
+  asm volatile("s_mov_b32 %0, m0\n\t" PIECES "s_mov_b32 m0, %0" : "=&s"(keep) : "s"(base), "s"(l0), "v"(v) : "memory", "scc")
+#define DRT_HP0 DRT_HALF_PIECE(0, 0)
+#define DRT_HP1 DRT_HP0 DRT_HALF_PIECE(3840, 256)
+#define DRT_HP2 DRT_HP1 DRT_HALF_PIECE(7680, 512)
+#define DRT_HP3 DRT_HP2 DRT_HALF_PIECE(11520, 768)
+#define DRT_HP4 DRT_HP3 DRT_HALF_PIECE(15360, 1024)
+#define DRT_HP5 DRT_HP4 DRT_HALF_PIECE(19200, 1280)
+    if constexpr (G == 1) DRT_HALF_ISSUE(DRT_HP0);
+    else if constexpr (G == 2) DRT_HALF_ISSUE(DRT_HP1);
+    else if constexpr (G == 3) DRT_HALF_ISSUE(DRT_HP2);
+    else if constexpr (G == 4) DRT_HALF_ISSUE(DRT_HP3);
+    else if constexpr (G == 5) DRT_HALF_ISSUE(DRT_HP4);
+    else DRT_HALF_ISSUE(DRT_HP5);
+#undef DRT_HP5
+#undef DRT_HP4
+#undef DRT_HP3
+#undef DRT_HP2
+#undef DRT_HP1
+#undef DRT_HP0
+#undef DRT_HALF_ISSUE
+#undef DRT_HALF_PIECE
+  }
+};
+
 template <int N>
 __device__ __forceinline__ void wait_tiles_younger(int younger) {
   // this wave has `younger` tiles issued after the one it needs; each is N instructions
@@ -802,11 +867,26 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
 // runs after the next tile's MFMAs are issued (two accumulator sets alternate), as in ip_scan16r.
 // Every score is the same 24-step 16x16x32 chain as ip_scan16r's: identical values and hits.
 // Ring protocol: ONE wait + work-group barrier per PAIR of tiles (it, it+1), it even; slot of tile t is
-// t mod 6; the tile at loop index j refills slot(j-2) with tile j+4, a quarter into its MFMAs.
-//   At the pair's barrier a wave has issued tiles .. it+3 and lets one tile (it+3) stay outstanding
-//   (vmcnt), so its shares of it+1 and it+2 have landed (it+2: the last RD k-steps of it+1 read its
-//   first fragments; tile it was certified by the pair before).  The barrier certifies
-//     RAW: every wave's share of tiles it+1 and it+2 has landed;
+// t mod 6; the tile at loop index j refills slot(j-2) with tile j+4 early in its MFMAs.
+//   Who issues a tile (loader half; widths with a multiple of four DMA pieces per tile: d = 128, 256,
+//   .. 768): waves 4-7, one per SIMD -- wave w and w+4 share a SIMD, and waves 4-7 are the ones that run
+//   at s_setprio 1.  They issue every tile WHOLE (HalfTile: 6 pieces per wave at d = 768), in the
+//   prologue and in the loop alike, at k-step KS/12 (2 at d = 768); waves 0-3 issue no DMA at all and
+//   keep the SIMD's matrix pipe fed while their partner issues.  Measured at d = 768 (profiles/r12a):
+//   ahead of the eight-wave issue in every run; the halves taking turns (tile t by half t & 1), waves
+//   0-3 as the loaders, the pieces spread over k-steps and a raised priority for the burst all slower.
+//   The short last tile of a shard is issued the same way (HalfTile clamps the source row), so a loader
+//   wave has G pieces in flight per tile and the other waves none.
+//   The other widths (d = 64, 192, 320, ..: 2, 6, 10, .. pieces) keep the eight-wave issue at k-step
+//   KS/4 (LeanTile: every wave GLDS_PER_WAVE pieces of every tile, duplicates for the remainder); for
+//   them read "every wave" for "a loader wave" below.
+//   At the pair's barrier (before even loop index it) tiles .. it+3 have been issued:
+//     a loader wave waits for all but its newest tile, vmcnt(G): it+1 and it+2 have landed, it+3 may
+//       stay outstanding; where it+3 does not exist (it+3 >= my_tiles) it waits for everything;
+//     waves 0-3 hold no tile: their wait is vmcnt(0) (their own hit stores at most).
+//   (it+2 must have landed because the last RD k-steps of it+1 read its first fragments; tile it was
+//   certified by the pair before.)  The barrier certifies
+//     RAW: every loader's share of tiles it+1 and it+2 has landed;
 //     WAR: every wave has issued all MFMAs of tiles it-2 and it-1, hence finished reading those slots
 //          (each MFMA waited for its own fragment) -- they are refilled with it+4 (during tile it) and
 //          it+5 (during it+1).  Both refills are legal from the barrier on; one per tile keeps the
@@ -816,9 +896,11 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
 //   seven at every tile.
 //   Slot census during a pair: it-2, it-1 refilling (tiles it+4, it+5); it, it+1 being read; it+2
 //   landed; it+3 in flight = 6.  A tile is issued >= 2 tile times before the barrier that needs it.
-//   Prologue: tiles 0 .. 3 issued, 0 .. 2 waited for, barrier (= pair 0's).  Every wave of a block runs
+//   Prologue: tiles 0 .. 3 issued (by the loader waves), 0 .. 2 waited for by the rule above with it = 0
+//   (all but tile 3 where it exists), barrier (= pair 0's).  Every wave of a block runs
 //   1 + (my_tiles - 1) / 2 barriers (my_tiles is block-uniform); no DMA is issued for a tile index >=
-//   my_tiles (do_dma); near the end of a block the wait is for everything outstanding.
+//   my_tiles (do_dma: it + 4 < my_tiles, in a loader wave); near the end of a block the wait is for
+//   everything outstanding.
 // ---------------------------------------------------------------------------
 template <int D>
 struct Scan32Cfg {
@@ -871,6 +953,11 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   if (my_tiles == 0) return;
   const int partial_tile = ((a.nrows & (kT16 - 1)) != 0 && (tall - 1) % tmul == tph) ? ntiles - 1 : -1;
   const uint32_t ring = lds_addr_of(smem);
+  // loader half (header comment): waves 4-7 issue every tile whole; the other widths, every wave its share
+  constexpr bool HALVES = HalfTile<D>::kOk;
+  constexpr int GW = HALVES ? HalfTile<D>::G : C::GLDS_PER_WAVE;   // pieces a loader has in flight per tile
+  constexpr int KDMA = HALVES ? KS / 12 : KS / 4;                  // the refill's k-step
+  const bool loader = !HALVES || wave >= NW / 2;
   const int64_t tile_stride = (int64_t)tstep * tmul * kT16 * a.ldp * 2;
   const char* next_base = (const char*)(a.P + ((int64_t)t0 * tmul + tph) * kT16 * a.ldp);
 
@@ -905,20 +992,30 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   LeanTile<D, NW> lt;
-  lt.init(a, wave, lane);
+  HalfTile<D> ht;
+  if constexpr (HALVES) ht.init(a, wave, lane);
+  else lt.init(a, wave, lane);
+  // a loader wave's issue of block tile `tile` into ring slot `slot`
+  auto issue = [&](int slot, int tile) {
+    if constexpr (HALVES)
+      ht.issue(a, ring + slot * C::TILE_BYTES, next_base, tile == partial_tile, tile * tmul + tph, wave, lane);
+    else
+      lt.template issue<false>(a, ring + slot * C::TILE_BYTES, next_base, tile == partial_tile, tile * tmul + tph,
+                               wave, lane);
+    next_base += tile_stride;
+  };
+  // the wait before a pair's barrier (it even; it = 0: the prologue's)
+  auto pair_wait = [&](int it) {
+    if (loader && it + PD <= my_tiles) wait_vmcnt<GW>();
+    else wait_vmcnt<0>();
+  };
 #pragma unroll
   for (int p = 0; p < PD; ++p) {
-    if (p < my_tiles) {
-      const int tile = t0 + p * tstep;
-      lt.template issue<false>(a, ring + p * C::TILE_BYTES, next_base, tile == partial_tile, tile * tmul + tph, wave,
-                               lane);
-      next_base += tile_stride;
-    }
+    if (p < my_tiles && loader) issue(p, t0 + p * tstep);
   }
   if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   // tiles 0 .. 2 landed (tile 3 may stay outstanding): this is also the first pair's barrier
-  if (PD <= my_tiles) wait_vmcnt<C::GLDS_PER_WAVE>();
-  else wait_vmcnt<0>();
+  pair_wait(0);
   lds_barrier();
 
   const int sw = (r >> 1) & 7;
@@ -964,14 +1061,13 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
 
   int buf = 0;   // slot of tile it
   // the pair's one synchronisation point, before its first (even) tile `it`.  Issued so far: tiles
-  // .. it+3.  This wave's shares of tiles it+1 and it+2 must have landed (one tile, it+3, may stay
-  // outstanding; near the end of the block nothing younger than it+2 was issued: wait for all).  After
-  // the barrier every wave's share of them has landed, and every wave has issued the MFMAs of tiles
-  // it-2 and it-1 (so its reads of those two slots completed: each MFMA waited for its own fragment)
-  // -- the two slots the pair refills
+  // .. it+3.  What this wave issued of tiles it+1 and it+2 must have landed (a loader lets its newest
+  // tile, it+3, stay outstanding; near the end of the block nothing younger than it+2 was issued: wait
+  // for all; waves 0-3 issued none of them).  After the barrier every loader's share of
+  // them has landed, and every wave has issued the MFMAs of tiles it-2 and it-1 (so its reads of those
+  // two slots completed: each MFMA waited for its own fragment) -- the two slots the pair refills
   auto pair_sync = [&](int it) {
-    if (it + PD <= my_tiles) wait_vmcnt<C::GLDS_PER_WAVE>();
-    else wait_vmcnt<0>();
+    pair_wait(it);
     lds_barrier();
   };
   // one tile: ring refill, MFMAs (+ the rolled reads), then the epilogue of the PREVIOUS tile (its
@@ -985,8 +1081,11 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
     // the barrier: round 5, 2.89-2.91 vs 2.95-2.97 ms per grouped launch in three alternating rounds,
     // profiles/r05y).  Counted from the pair's first tile e, that tile refills slot(e-2) and the
     // second one slot(e-1): both free since the pair's barrier; one refill per tile keeps the issue
-    // spread (both in the first tile measured slower, profiles/r11a)
-    const bool do_dma = it + PD < my_tiles;
+    // spread (both in the first tile measured slower, profiles/r11a).  Loader half: the refill is the
+    // whole tile from waves 4-7; their SIMD partners issue none and keep issuing MFMAs meanwhile, so it
+    // can go earlier: k-step KS/12 (k-steps 0 .. 12 at d = 768 in profiles/r12a; one wave-uniform test
+    // per tile, as before)
+    const bool do_dma = it + PD < my_tiles && loader;
     const int ntile = tile + PD * tstep;
     const int pslot = buf < 2 ? buf + NB - 2 : buf - 2;   // slot of tile it-2 (it < 2: a slot not yet used)
     const int nslot = buf + 1 == NB ? 0 : buf + 1;
@@ -999,11 +1098,7 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
       // fragment s + RD: of this tile, or (the last RD steps) the first ones of tile it+1
       af[s % RD] = s + RD < KS ? frag(buf, s + RD) : frag(nslot, s + RD - KS);
       __builtin_amdgcn_sched_barrier(0);
-      if (s == KS / 4 && do_dma) {
-        lt.template issue<false>(a, ring + pslot * C::TILE_BYTES, next_base, ntile == partial_tile,
-                                 ntile * tmul + tph, wave, lane);
-        next_base += tile_stride;
-      }
+      if (s == KDMA && do_dma) issue(pslot, ntile);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (it > 0) epilogue(prev0, prev1, rb_prev);
