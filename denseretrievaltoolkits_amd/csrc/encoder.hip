@@ -9,7 +9,8 @@
 //                   with v_mfma_f32_32x32x16_bf16, online softmax over 32-key
 //                   tiles; S^T = K Q^T keeps each query's scores lane-local and
 //                   the S^T accumulator feeds the P.V MFMA directly as its B
-//                   operand (no LDS round trip for P)
+//                   operand (no LDS round trip for P); the RB instantiations add T5's
+//                   relative-position bias to the scores (drt_attention_relbias_bf16)
 //   pool            first / masked-mean / masked-max pooling (utils.py:233-240)
 //   l2norm          F.normalize(reps, dim=1) (biencoder.py:149-150)
 #include "drt_common.h"
@@ -194,20 +195,6 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const __bf16* X, in
   }
 }
 
-// Work-groups of the row-looping LayerNorm: 8 per CU (32 waves), at most one per 4 rows.
-static unsigned ln_rows_grid(int64_t M) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-              ? v
-              : 256;
-  }
-  const int64_t need = (M + 3) / 4, cap = (int64_t)cus * 8;
-  return (unsigned)(need < cap ? need : cap);
-}
-
 // ---------------------------------------------------------------------------
 // Attention.  One work-group (4 waves) per (sequence b, head hd); wave w owns
 // query blocks w, w+4, ... of 32 rows.  K is staged in LDS as swizzled
@@ -231,6 +218,8 @@ struct AttnArgs {
   uint64_t seed, site;    //   keep = attn_keep(attn_row_key(seed, site, (b * heads + head) * L + q), key)
   uint32_t* drop_bits;    // optional [B][heads][L][ceil(L / 32)]: the keep mask, bit (key & 31) of word
                           //   (query, key >> 5) -- the backward reads it instead of re-hashing
+  const float* relbias;   // RB kernels: [heads][2 L - 1] fp32, entry (head, key - query + L - 1) is added
+                          //   to the score of (query, key) before the softmax (T5's relative-position bias)
 };
 
 // Attention forward, one work-group per (sequence, head): K (swizzled rows), V^T and the key bias
@@ -256,7 +245,12 @@ constexpr float kLn2 = 0.6931471805599453f;
 
 // Register budget: 4 waves per SIMD (<= 128 VGPRs) -- at 5 query blocks the LDS (42 KiB) admits 3
 // work-groups of 5 waves per CU, i.e. 4 waves on three of the SIMDs.
-template <int NB, bool DROP>
+// RB (T5, modeling_t5.py T5Attention): the head's 2 Lp relative-position biases sit in LDS behind
+// kb[], pre-multiplied by log2 e (entries past 2 L - 2 are 0); query q reads them at key + L - 1 - q,
+// so the 32 query rows of each half of a wave read consecutive banks.  The bias joins kb before the
+// fma: a masked key stays at -FLT_MAX (the bias is absorbed, as in HF's fp32 sum), a padding key at
+// -inf, and an all-zero table leaves every bit of the !RB kernel's result.
+template <int NB, bool DROP, bool RB = false>
 __global__ __launch_bounds__(NB == 5 ? 320 : 256) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void attention_fwd_kernel(AttnArgs a) {
   constexpr int NW = NB == 5 ? 5 : 4;
@@ -269,6 +263,7 @@ void attention_fwd_kernel(AttnArgs a) {
   char* Ks = smem;                          // Lp * 128 B
   char* Vt = smem + Lp * 128;               // 64 * vts B
   float* kb = (float*)(Vt + 64 * vts);      // Lp floats
+  float* rb = kb + Lp;                      // RB: 2 Lp floats
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
@@ -331,6 +326,10 @@ void attention_fwd_kernel(AttnArgs a) {
     else if (a.mask && a.mask[b * a.L + i] == 0) bv = -3.402823466e+38f;  // (1 - mask) * finfo.min
     kb[i] = bv;
   }
+  if (RB) {
+    const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
+    for (int i = tid; i < 2 * Lp; i += NT) rb[i] = i < 2 * L - 1 ? src[i] * kLog2e : 0.0f;
+  }
   __syncthreads();
 
   // per-lane LDS offsets (a 32-key tile starts at a multiple of 32 rows: its swizzle term never
@@ -357,6 +356,7 @@ void attention_fwd_kernel(AttnArgs a) {
       qf[s] = v;
     }
     const uint32_t rowkey = DROP ? attn_row_key(a.seed, a.site, (uint64_t)(hrow + qq)) : 0u;
+    const float* rbq = rb + (L - 1 - qrow);    // RB: this query's bias of key k is rbq[k], k < Lp
     uint32_t words[NB ? NB : 1];               // keep words of this query (stored once, after the last tile)
     f32x16 o[2];
 #pragma unroll
@@ -380,7 +380,11 @@ void attention_fwd_kernel(AttnArgs a) {
       const f32x2 l2e = {kLog2e, kLog2e};
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const f32x4 kbv = *(const f32x4*)(kb + kt + 8 * g + 4 * h);
+        f32x4 kbv = *(const f32x4*)(kb + kt + 8 * g + 4 * h);
+        if (RB) {   // 4-B reads: the offset L - 1 - q is aligned to nothing wider
+          const float* rp = rbq + kt + 8 * g + 4 * h;
+          kbv += f32x4{rp[0], rp[1], rp[2], rp[3]};
+        }
         const f32x2 lo = __builtin_elementwise_fma(f32x2{s[4 * g], s[4 * g + 1]}, l2e, f32x2{kbv[0], kbv[1]});
         const f32x2 hi = __builtin_elementwise_fma(f32x2{s[4 * g + 2], s[4 * g + 3]}, l2e, f32x2{kbv[2], kbv[3]});
         s[4 * g] = lo[0];
@@ -761,6 +765,37 @@ int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void
       break;
   }
 #undef DRT_AF_LAUNCH
+  return hip_status(hipGetLastError());
+}
+
+// The inference forward with a relative-position bias (T5Attention, modeling_t5.py: scores =
+// q k^T + position_bias, no 1 / sqrt(d) -- the caller passes scale = 1): relbias fp32
+// [heads][2 L - 1], entry (head, key - query + L - 1).  The RB instantiations of the kernel above.
+int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx, int64_t B,
+                               int64_t L, int32_t heads, int32_t head_dim, float scale, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
+  if (B == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx && relbias);
+  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, nullptr, 0.0f, 0, 0,
+             nullptr, relbias};
+  const int Lp = ((int)L + 31) & ~31;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (size_t)Lp * 8;
+  static bool attr_set = false;
+  if (!attr_set) {   // L > 224 stages more than the default 64 KiB (only the NB = 0 kernel gets there)
+    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)attention_fwd_kernel<0, false, true>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  const dim3 grid((unsigned)(B * heads));
+  hipStream_t s = (hipStream_t)stream;
+  switch (Lp / 32) {
+    case 1: hipLaunchKernelGGL((attention_fwd_kernel<1, false, true>), grid, dim3(256), lds, s, a); break;
+    case 2: hipLaunchKernelGGL((attention_fwd_kernel<2, false, true>), grid, dim3(256), lds, s, a); break;
+    case 3: hipLaunchKernelGGL((attention_fwd_kernel<3, false, true>), grid, dim3(256), lds, s, a); break;
+    case 4: hipLaunchKernelGGL((attention_fwd_kernel<4, false, true>), grid, dim3(256), lds, s, a); break;
+    case 5: hipLaunchKernelGGL((attention_fwd_kernel<5, false, true>), grid, dim3(320), lds, s, a); break;
+    default: hipLaunchKernelGGL((attention_fwd_kernel<0, false, true>), grid, dim3(256), lds, s, a); break;
+  }
   return hip_status(hipGetLastError());
 }
 

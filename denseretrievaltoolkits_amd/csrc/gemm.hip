@@ -123,8 +123,10 @@ __device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
 // EPI_DGELU: multiply by GELU'(R) (the dgrad of a GELU input: R = the bf16 pre-activation);
 // EPI_PRE: also store the pre-activation to C2 (the training forward keeps it for the backward);
 // EPI_DROP: dropout (counter hash of the flat output index, the mask drt_dropout_add_bf16 draws)
-// applied after bias / GELU, before the residual.
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_DGELU = 8, EPI_PRE = 16, EPI_DROP = 32 };
+// applied after bias / GELU, before the residual;
+// EPI_RELU: max(x, 0) where EPI_GELU applies its GELU (T5DenseActDense; never both).
+enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_GELU = 2, EPI_RESID = 4, EPI_DGELU = 8, EPI_PRE = 16, EPI_DROP = 32,
+       EPI_RELU = 64 };
 constexpr int EPI_AUX = EPI_RESID | EPI_DGELU;   // epilogues that read R
 
 // d/dx [x Phi(x)] = Phi(x) + x phi(x), erf by Abramowitz & Stegun 7.1.26 as gelu_fast
@@ -292,6 +294,7 @@ __global__ __launch_bounds__(kGemmThreads, NS == 2 ? 2 : 1) void gemm_nt_kernel(
           float v = acc[i][j][e] * a.alpha + bv;
           if (EPI & EPI_PRE) ((__bf16*)a.C2)[row * a.ldc + col] = (__bf16)v;
           if (EPI & EPI_GELU) v = gelu_erf(v);
+          if (EPI & EPI_RELU) v = fmaxf(v, 0.0f);
           v = epi_post<EPI>(a, v, row, col, aux[j][i][e]);
           if (OUT_BF16) ((__bf16*)a.C)[row * a.ldc + col] = (__bf16)v;
           else ((float*)a.C)[row * a.ldc + col] = v;
@@ -314,6 +317,7 @@ __global__ __launch_bounds__(kGemmThreads, NS == 2 ? 2 : 1) void gemm_nt_kernel(
         float v = acc[i][j][e] * a.alpha + bv;
         if (EPI & EPI_PRE) ((__bf16*)a.C2)[row * a.ldc + col] = (__bf16)v;
         if (EPI & EPI_GELU) v = gelu_erf(v);
+        if (EPI & EPI_RELU) v = fmaxf(v, 0.0f);
         v = epi_post<EPI>(a, v, row, col, (EPI & EPI_AUX) ? (float)a.R[row * a.ldr + col] : 0.f);
         if (OUT_BF16) ((__bf16*)a.C)[row * a.ldc + col] = (__bf16)v;
         else ((float*)a.C)[row * a.ldc + col] = v;
@@ -352,6 +356,7 @@ __global__ __launch_bounds__(256) void splitk_epi_kernel(GemmArgs a, int splits)
       if (EPI & EPI_BIAS) x += a.bias[col + q];
       if (EPI & EPI_PRE) ((__bf16*)a.C2)[row * a.ldc + col + q] = (__bf16)x;
       if (EPI & EPI_GELU) x = gelu_erf(x);
+      if (EPI & EPI_RELU) x = fmaxf(x, 0.0f);
       x = epi_post<EPI>(a, x, row, col + q, (EPI & EPI_AUX) ? (float)a.R[row * a.ldr + col + q] : 0.f);
       if (OUT_BF16) ((__bf16*)a.C)[row * a.ldc + col + q] = (__bf16)x;
       else ((float*)a.C)[row * a.ldc + col + q] = x;
@@ -643,6 +648,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& a, f32x4 (&acc)[8][4
         float x = acc[i][j][u] * a.alpha + ((EPI & EPI_BIAS) ? a.bias[col + u] : 0.f);
         if (EPI & EPI_PRE) ((__bf16*)a.C2)[row * a.ldc + col + u] = (__bf16)x;
         if (EPI & EPI_GELU) x = gelu_erf(x);
+        if (EPI & EPI_RELU) x = fmaxf(x, 0.0f);
         x = epi_post<EPI>(a, x, row, col + u, (EPI & EPI_AUX) ? (float)a.R[row * a.ldr + col + u] : 0.f);
         if (OUT_BF16) ((__bf16*)a.C)[row * a.ldc + col + u] = (__bf16)x;
         else ((float*)a.C)[row * a.ldc + col + u] = x;
@@ -684,6 +690,7 @@ __device__ __forceinline__ void pp_epilogue_lds(const GemmArgs& a, f32x4 (&acc)[
           for (int u = 0; u < 4; u += 2) {   // element pairs: the GELU on packed fp32 math
             f32x2 x = {acc[i][j][u] * a.alpha + bv[j][u], acc[i][j][u + 1] * a.alpha + bv[j][u + 1]};
             if ((EPI & EPI_GELU) && act) x = gelu_fast2(x);
+            if ((EPI & EPI_RELU) && act) x = f32x2{fmaxf(x.x, 0.0f), fmaxf(x.y, 0.0f)};
             o[u] = (__bf16)x.x;
             o[u + 1] = (__bf16)x.y;
           }
@@ -735,6 +742,7 @@ __device__ __forceinline__ void pp_epilogue_lds(const GemmArgs& a, f32x4 (&acc)[
             if ((EPI & EPI_PRE) && m0 + grp * 128 + h * 64 + r < a.m)
               ((__bf16*)a.C2)[(m0 + grp * 128 + h * 64 + r) * a.ldc + colw + j * 16 + 4 * fc + u] = (__bf16)x;
             if (EPI & EPI_GELU) x = gelu_fast(x);
+            if (EPI & EPI_RELU) x = fmaxf(x, 0.0f);
             v[u] = x;
           }
           const int chunk = (j * 4 + fc) ^ (r & 7);
@@ -1157,6 +1165,11 @@ int launch_gemm(const GemmArgs& a, bool out_bf16, int epi, size_t ws_bytes, hipS
     case EPI_BIAS | EPI_GELU | EPI_PRE: return launch_gemm_t<true, EPI_BIAS | EPI_GELU | EPI_PRE>(a, ws_bytes, s);
     case EPI_DGELU: return launch_gemm_t<true, EPI_DGELU>(a, ws_bytes, s);
     case EPI_BIAS | EPI_DROP | EPI_RESID: return launch_gemm_t<true, EPI_BIAS | EPI_DROP | EPI_RESID>(a, ws_bytes, s);
+    // T5 FFN1 (drt_linear_bf16* flag bit 3)
+    case EPI_RELU: return launch_gemm_t<true, EPI_RELU>(a, ws_bytes, s);
+    case EPI_BIAS | EPI_RELU: return launch_gemm_t<true, EPI_BIAS | EPI_RELU>(a, ws_bytes, s);
+    case EPI_RELU | EPI_RESID: return launch_gemm_t<true, EPI_RELU | EPI_RESID>(a, ws_bytes, s);
+    case EPI_BIAS | EPI_RELU | EPI_RESID: return launch_gemm_t<true, EPI_BIAS | EPI_RELU | EPI_RESID>(a, ws_bytes, s);
     default: return DRT_EINVAL;
   }
 }
@@ -1195,8 +1208,9 @@ extern "C" int drt_linear_bf16_ws(const void* X, const void* W, const float* bia
                                   int64_t M, int64_t N, int64_t K, int32_t flags, void* ws, size_t ws_bytes,
                                   void* stream);
 
-// nn.Linear: Y[M, N] = X[M, K] . W[N, K]^T (+ bias) (GELU) (+ residual [M, N] bf16)
-// flags: DRT_LIN_GELU = 1, DRT_LIN_OUT_F32 = 2.
+// nn.Linear: Y[M, N] = X[M, K] . W[N, K]^T (+ bias) (GELU | ReLU) (+ residual [M, N] bf16)
+// flags: DRT_LIN_GELU = 1, DRT_LIN_OUT_F32 = 2, DRT_LIN_RELU = 8 (bf16 output only, not with GELU;
+// the residual is added after it).
 extern "C" int drt_linear_bf16(const void* X, const void* W, const float* bias, const void* residual, void* Y,
                                int64_t M, int64_t N, int64_t K, int32_t flags, void* stream) {
   return drt_linear_bf16_ws(X, W, bias, residual, Y, M, N, K, flags, nullptr, 0, stream);
@@ -1206,9 +1220,10 @@ extern "C" int drt_linear_bf16_ws(const void* X, const void* W, const float* bia
                                   int64_t M, int64_t N, int64_t K, int32_t flags, void* ws, size_t ws_bytes,
                                   void* stream) {
   DRT_REQUIRE(M >= 0 && N > 0 && K > 0 && K % 64 == 0);
+  const bool gelu = flags & 1, f32 = flags & 2, relu = flags & 8;
+  DRT_REQUIRE(!(relu && (gelu || f32)));
   if (M == 0) return DRT_OK;
   DRT_REQUIRE(X && W && Y);
-  const bool gelu = flags & 1, f32 = flags & 2;
   DRT_REQUIRE(!(gelu && residual));
   GemmArgs a{};
   a.A = (const __bf16*)X;
@@ -1225,7 +1240,7 @@ extern "C" int drt_linear_bf16_ws(const void* X, const void* W, const float* bia
   a.ldr = N;
   a.alpha = 1.0f;
   a.ws = (float*)ws;
-  const int epi = (bias ? EPI_BIAS : 0) | (gelu ? EPI_GELU : 0) | (residual ? EPI_RESID : 0);
+  const int epi = (bias ? EPI_BIAS : 0) | (gelu ? EPI_GELU : 0) | (relu ? EPI_RELU : 0) | (residual ? EPI_RESID : 0);
   return launch_gemm(a, !f32, epi, ws ? ws_bytes : 0, (hipStream_t)stream);
 }
 

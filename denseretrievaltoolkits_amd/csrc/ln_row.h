@@ -64,4 +64,19 @@ __device__ __forceinline__ void ln_row_gb(float (&x)[EPL], const float (&g)[EPL]
   }
 }
 
+// Work-groups of the row-looping norms (layernorm_bf16_kernel, rmsnorm_bf16_kernel): 8 per CU
+// (32 waves), at most one per 4 rows.
+inline unsigned ln_rows_grid(int64_t M) {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, v = 0;
+    cus = (hipGetDevice(&dev) == hipSuccess &&
+           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+              ? v
+              : 256;
+  }
+  const int64_t need = (M + 3) / 4, cap = (int64_t)cus * 8;
+  return (unsigned)(need < cap ? need : cap);
+}
+
 }  // namespace drt

@@ -8,7 +8,9 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   _encoding_corpus, DRModelForInference) runs the whole tower on the HIP inference
   kernels (model/encoder.HipBertEncoder): bf16 MFMA GEMMs, fused attention, fp32
   LayerNorm statistics, pooling / head / L2-normalise kernels.  ``hidden`` is
-  returned in bf16, ``reps`` in fp32.
+  returned in bf16, ``reps`` in fp32.  ``encoder_only`` T5 towers (T5EncoderModel)
+  take the same path through model/t5_encoder.HipT5Encoder; with autograd they
+  stay on the HF module.
 * encode with autograd (training, or eval mode with grad on, where the reference
   returns differentiable reps) runs BERT towers up to L = 512 on the HIP training
   tower (model/train_tower.py: forward with saved bf16 activations + backward on
@@ -36,6 +38,7 @@ from transformers import AutoModel, BatchEncoding, PreTrainedModel
 from transformers.modeling_outputs import ModelOutput
 
 from .encoder import HipBertEncoder, l2_normalize_, linear_head
+from .t5_encoder import HipT5Encoder, t5_supported
 from .train_tower import MAX_TRAIN_SEQ, tower_supported, train_hidden
 from .linear import LinearHead
 
@@ -148,16 +151,23 @@ class DRModel(nn.Module):
         return DROutput(loss=loss, scores=scores, q_reps=q_reps, p_reps=p_reps)
 
     # ------------------------------------------------------------------
-    def _hip_encoder(self, model) -> HipBertEncoder:
+    def _hip_encoder(self, model):
+        """HipBertEncoder / HipT5Encoder snapshot of the tower, rebuilt when a parameter changes."""
         dev = next(model.parameters()).device
         key = id(model)
         ver = tuple(p._version for p in model.parameters()) + (str(dev),)
         hit = self._hip_cache.get(key)
         if hit is None or hit[0] != ver:
-            if type(model).__name__ not in ("BertModel",):
-                raise NotImplementedError(
-                    f"HIP encoder supports BERT-family towers only (got {type(model).__name__})")
-            enc = HipBertEncoder.from_hf(model, dev)
+            name = type(model).__name__
+            if name == "BertModel":
+                enc = HipBertEncoder.from_hf(model, dev)
+            elif name == "T5EncoderModel":
+                why = t5_supported(model)
+                if why is not None:
+                    raise NotImplementedError(f"HIP T5 encoder: {why}")
+                enc = HipT5Encoder.from_hf(model, dev)
+            else:
+                raise NotImplementedError(f"HIP encoder supports BERT-family towers only (got {name})")
             self._hip_cache[key] = (ver, enc)
             return enc
         return hit[1]

@@ -347,7 +347,8 @@ int drt_gemm_nt_bf16_f32(const void* A, const void* B, float* C, int64_t m, int6
  *   + pos_emb[l]) (modeling_bert.py:53-107); tables/LN params fp32, H % 256 == 0.
  * drt_linear_bf16: Y = X . W^T (+bias)(GELU)(+residual); X [M,K], W [N,K] bf16,
  *   bias fp32 [N] or NULL, residual bf16 [M,N] or NULL; flags bit0 = GELU(erf),
- *   bit1 = fp32 output (else bf16).  K % 64 == 0.
+ *   bit1 = fp32 output (else bf16), bit3 = ReLU (after the bias, before the
+ *   residual; bf16 output only, not with GELU).  K % 64 == 0.
  * drt_layernorm_f32_bf16: out bf16 = LN(X fp32 [M,H]).
  * drt_layernorm_bf16: out bf16 = LN(X bf16 [M,H]) (fp32 statistics); the
  *   encoder's default, fed by a bf16 +bias +residual epilogue (one rounding).
@@ -530,6 +531,32 @@ int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const vo
 int drt_pool_bf16(const void* hidden, const int64_t* mask, int64_t B, int64_t L, int32_t H,
                   int32_t mode, float* out, void* out_bf16, void* stream);
 int drt_l2_normalize_f32(float* x, int64_t B, int32_t H, void* out_bf16, void* stream);
+/* ------------------------------------------------------------------------
+ * T5 encoder forward building blocks (HF T5EncoderModel in eval mode, modeling_t5.py; pre-norm
+ * layer = rmsnorm -> linear(QKV, no bias) -> attention + relative bias -> linear(out, +residual)
+ * -> rmsnorm -> linear(FFN1, ReLU | gated gelu_new) -> linear(FFN2, +residual); final rmsnorm).
+ * Stream-ordered, no allocation; DRT_EINVAL for a bad shape before any HIP call.
+ * ------------------------------------------------------------------------
+ * drt_t5_embed_bf16: out[B*L, H] bf16 = table[ids] (fp32 [vocab, H], H % 4 == 0): the
+ *   residual stream's first value, no position / type table and no norm.
+ * drt_rmsnorm_bf16: out bf16 = X * rsqrt(mean(X^2) + eps) * weight over bf16 X [M, H] (T5LayerNorm:
+ *   fp32 sum of squares, no mean, no bias, one rounding); H % 256 == 0, H <= 1024; out may alias X.
+ * drt_attention_relbias_bf16: drt_attention_bf16 with relbias fp32 [heads][2L-1]: entry
+ *   (h, k - q + L - 1) is added to the score of query q and key k before the softmax (T5 passes
+ *   scale = 1).  A masked key keeps finfo.min (the bias is absorbed), so a sequence with every key
+ *   masked gets the uniform softmax; an all-zero table gives drt_attention_bf16's bits.
+ *   L <= 512, head_dim == 64; qkv [B*L, 3*heads*64], ctx [B*L, heads*64].
+ * drt_gated_gelu_new_bf16: out[M, F] bf16 = gelu_new(X[:, :F]) * X[:, F:] over bf16 X [M, 2F]
+ *   (T5DenseGatedActDense after one GEMM over [wi_0; wi_1]); fp32 math, one rounding; F % 8 == 0,
+ *   X and out 16-byte aligned.                                                                   */
+int drt_t5_embed_bf16(const int64_t* ids, int64_t B, int64_t L, const float* table, int32_t H,
+                      void* out, void* stream);
+int drt_rmsnorm_bf16(const void* X, int64_t M, int32_t H, const float* weight, float eps,
+                     void* out, void* stream);
+int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx,
+                               int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
+                               void* stream);
+int drt_gated_gelu_new_bf16(const void* X, int64_t M, int64_t F, void* out, void* stream);
 /* ------------------------------------------------------------------------
  * In-batch-negative training loss (DRModel.forward, biencoder.py:107-119;
  * SimpleContrastiveLoss, losses.py:11-17), fp32 like the reference.
