@@ -141,6 +141,9 @@ _SIGNATURES = [
     ("drt_rmsnorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
     ("drt_attention_relbias_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     ("drt_gated_gelu_new_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
+    ("drt_t5_head_expand_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
+    ("drt_t5_cross_pool_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
+    ("drt_t5_head_reduce_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     ("drt_gemm_nt_f32", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     ("drt_gemm_f32", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
     ("drt_ce_fwd", c_i32, [c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp]),

@@ -7,8 +7,15 @@ tower runs on the HIP inference kernels (the same bf16 MFMA GEMMs + fused
 attention as the bi-encoder) and the 768 -> 1 head on the HIP GEMM; with grad on
 (training, or eval mode with grad) BERT pair towers up to L = 512 run on the HIP
 training tower (model/train_tower.py, forward + backward on HIP kernels, HF
-train-mode dropout), other towers on the HF module under autograd.  T5
-rerankers (logits of pos/neg tokens, :115-119) are outside the MI355X path.
+train-mode dropout), other towers on the HF module under autograd.
+
+T5 rerankers (monoT5, :115-119: ``T5ForConditionalGeneration`` with ``decoder_input_ids = 0``,
+scores = ``logits[:, 0, [neg_token_id, pos_token_id]]``) follow the same rule: with no gradient to
+ask for, the encoder runs on ``HipT5Encoder`` and the single decoder step on the absorbed
+cross-attention kernels (model/t5_decoder.py, ``HipT5PairScorer``), returning [B, 2] fp32 in the
+reference's column order; with grad on, or on the CPU, the HF module computes exactly what the
+reference computes.  A configuration the kernels do not cover raises ``NotImplementedError`` on the
+no-grad GPU path.
 """
 from __future__ import annotations
 
@@ -27,6 +34,7 @@ from transformers.modeling_outputs import ModelOutput
 from ..trainer.losses import CrossEntropyLoss, rr_loss_functions
 from .encoder import HipBertEncoder, linear_head
 from .linear import LinearHead
+from .t5_decoder import HipT5PairScorer, t5_seq2seq_supported
 from .train_tower import MAX_TRAIN_SEQ, tower_supported, train_hidden
 
 logger = logging.getLogger(__name__)
@@ -37,6 +45,14 @@ class RROutput(ModelOutput):
     pos_pair_scores: Tensor = None
     neg_pair_scores: Tensor = None
     loss: Tensor = None
+
+
+def relevance(scores: Tensor) -> Tensor:
+    """One relevance column from RRModel.encode's scores: a T5 reranker's [B, 2] (neg, pos) logits
+    become monoT5's log_softmax(scores, -1)[:, 1] as [B, 1]; one-column scores pass through."""
+    if scores.dim() == 2 and scores.shape[1] == 2:
+        return torch.log_softmax(scores.float(), -1)[:, 1:2]
+    return scores
 
 
 class RRModel(nn.Module):
@@ -89,12 +105,37 @@ class RRModel(nn.Module):
             self._hip = (ver, enc, w)
         return self._hip[1], self._hip[2]
 
+    def _hip_t5_state(self):
+        dev = next(self.lm.parameters()).device
+        ver = tuple(p._version for p in self.lm.parameters()) + ("t5", str(dev))
+        if self._hip is None or self._hip[0] != ver:
+            why = t5_seq2seq_supported(self.lm)
+            if why is not None:
+                raise NotImplementedError(f"HIP T5 reranker: {why}")
+            self._hip = (ver, HipT5PairScorer.from_hf(self.lm, dev))
+        return self._hip[1]
+
+    def _encode_t5(self, items):
+        """reranker.py:115-119: one decoder step from token 0, logits of (neg_token, pos_token)."""
+        dev = next(self.lm.parameters()).device
+        tokens = (self.neg_token_id, self.pos_token_id)
+        frozen = not any(p.requires_grad for p in self.lm.parameters())
+        if dev.type == "cuda" and (not torch.is_grad_enabled() or frozen):
+            return self._hip_t5_state().logits(items["input_ids"], items.get("attention_mask"), tokens)
+        from .biencoder import _log_fallback
+        _log_fallback("T5 reranker: " + ("tower on the CPU" if dev.type != "cuda" else
+                                         "autograd on (the decoder step has no HIP backward)"))
+        ids = items["input_ids"]
+        start = ids.new_zeros((ids.shape[0], 1), dtype=torch.long)
+        logits = self.lm(**items, decoder_input_ids=start, return_dict=True).logits
+        return logits[:, 0, list(tokens)]
+
     def encode(self, items):
         if items is None:
             return None, None
         items = BatchEncoding(items)
         if "T5" in type(self.lm).__name__ and not getattr(self.model_args, "encoder_only", False):
-            raise NotImplementedError("T5 rerankers are outside the MI355X hot path")
+            return self._encode_t5(items)
         if self.pooling not in ("first", "mean"):
             raise ValueError("Unknown pooling type: {}".format(self.pooling))
         dev = next(self.lm.parameters()).device

@@ -50,13 +50,16 @@ def pack_pairs(query: Dict[str, Tensor], passage: Dict[str, Tensor], n_passages:
 def teacher_scores(rr_model, query: Dict[str, Tensor], passage: Dict[str, Tensor], n_passages: int,
                    pad_token_id: int, chunk: int = 256) -> Tensor:
     """[B, n] fp32 cross-encoder scores of every query's own passages (no autograd: RRModel.encode
-    takes the HIP inference tower), ``chunk`` pairs per tower pass."""
+    takes the HIP inference tower), ``chunk`` pairs per tower pass.  A T5 teacher's two columns
+    (neg, pos logits) are reduced to monoT5's relevance log_softmax(scores, -1)[:, 1]."""
+    from ..model.reranker import relevance
     pairs = pack_pairs(query, passage, n_passages, pad_token_id)
     rows = pairs["input_ids"].shape[0]
     out = []
     with torch.no_grad():
         for a in range(0, rows, int(chunk)):
-            out.append(rr_model.encode({k: v[a: a + chunk] for k, v in pairs.items()}).float().reshape(-1))
+            scores = rr_model.encode({k: v[a: a + chunk] for k, v in pairs.items()})
+            out.append(relevance(scores).float().reshape(-1))
     return torch.cat(out).view(rows // int(n_passages), int(n_passages))
 
 

@@ -537,6 +537,7 @@ class RRTrainer(Trainer):
         return self.model(pos_pairs=inputs[0], neg_pairs=inputs[1]).loss
 
     def evaluate(self, pair_loader, ep):
+        from ..model.reranker import relevance
         self.model.eval()
         a = self.training_args
         topk = a.topk if not isinstance(a.topk, str) else [int(x) for x in a.topk.split(",")]
@@ -564,7 +565,9 @@ class RRTrainer(Trainer):
             data = {k: self._to_device(v) for k, v in batch[1].items()}
             with torch.no_grad():
                 scores = m(pos_pairs=data, neg_pairs=None).detach()
-            cur = (batch,) + _stage_host(scores.float())
+            # a T5 reranker's (neg, pos) logits -> one relevance column, so the per-query sort below
+            # ranks by relevance (the reference keeps column 0, the neg_token logit)
+            cur = (batch,) + _stage_host(relevance(scores).float())
             if pend is not None:
                 finish(pend)
             pend = cur

@@ -557,6 +557,26 @@ int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float
                                int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
                                void* stream);
 int drt_gated_gelu_new_bf16(const void* X, int64_t M, int64_t F, void* out, void* stream);
+/* One-step T5 decoder (T5ForConditionalGeneration with a single decoder token: monoT5 rerankers).
+ * With one query per sequence the cross-attention runs in absorbed form over the encoder output
+ * enc [B, L, D] bf16 itself; no K / V projection of it is formed.  Wk, Wv: EncDecAttention.k / .v
+ * weights as HF stores them, bf16 [heads*64, D].  1 <= heads <= 16, D % 256 == 0, D <= 1024.
+ * drt_t5_head_expand_bf16: qt[b, h, :] = sum_j q[b, 64h+j] Wk[64h+j, :] over bf16 q [B, heads*64]
+ *   -> bf16 qt [B, heads, D]; fp32 accumulation, one rounding; Wk 16-byte and q 8-byte aligned.
+ * drt_t5_cross_pool_bf16: per (sequence, head) p = softmax_l(qt[b,h,:] . enc[b,l,:]) (no scale, no
+ *   bias) and pooled[b, h, :] = sum_l p_l enc[b, l, :], bf16 [B, heads, D]; enc is read once, the
+ *   softmax is online in fp32 (P rounded to bf16 for the MFMA, fp32 accumulators, one output
+ *   rounding).  mask int64 [B, L] or NULL with drt_attention_relbias_bf16's convention: a masked
+ *   key contributes nothing whatever finite value enc holds there, a sequence with every key masked
+ *   gets the uniform softmax over its L keys.  1 <= L <= 512; qt and enc 16-byte aligned.
+ * drt_t5_head_reduce_bf16: ctx[b, 64h+j] = Wv[64h+j, :] . pooled[b, h, :] -> bf16 ctx [B, heads*64];
+ *   fp32 accumulation, one rounding; pooled and Wv 16-byte aligned.                                */
+int drt_t5_head_expand_bf16(const void* q, const void* Wk, void* qt, int64_t B, int32_t heads,
+                            int32_t D, void* stream);
+int drt_t5_cross_pool_bf16(const void* qt, const void* enc, const int64_t* mask, void* pooled,
+                           int64_t B, int64_t L, int32_t heads, int32_t D, void* stream);
+int drt_t5_head_reduce_bf16(const void* pooled, const void* Wv, void* ctx, int64_t B, int32_t heads,
+                            int32_t D, void* stream);
 /* ------------------------------------------------------------------------
  * In-batch-negative training loss (DRModel.forward, biencoder.py:107-119;
  * SimpleContrastiveLoss, losses.py:11-17), fp32 like the reference.
