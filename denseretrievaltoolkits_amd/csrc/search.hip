@@ -49,6 +49,7 @@
 // kernels of steps 1-3; refine.hip step 5, its "Error bound", the wide resolve
 // and large k (both call launch_scan here); merge.hip the per-shard list merges.
 #include <cmath>
+#include <type_traits>
 
 #include "profile.h"
 #include "search_internal.h"
@@ -866,6 +867,22 @@ __global__ __launch_bounds__(512, 1) void ip_scan16r_kernel(ScanArgs a) {
 // during its own tile (and, its first RD fragments, at the end of the tile before).  A tile's epilogue
 // runs after the next tile's MFMAs are issued (two accumulator sets alternate), as in ip_scan16r.
 // Every score is the same 24-step 16x16x32 chain as ip_scan16r's: identical values and hits.
+// Hit check, per 16-query set and tile: 3 VALU instructions, a hazard pad and a branch when the set has no
+//   hit in the tile (s_nop 2, v_max3, v_max in one asm statement, then v_cmp mx >= tau; it was 7 VALU: two
+//   canonicalising self-maxima, a subtraction to compare with 0 and the row bound ahead of the branch).
+//   The pad is the statement's own, see there: the compiler pads nothing inside an asm statement.  With a
+//   hit, each of the lane's four rows is tested acc >= tau and balloted; the row bound (row < nrows) is
+//   tested only in the epilogue after the loop, the one place the shard's short last tile can be.  At the
+//   product's densities a third (passes 1-7, 233 hits per query) to more than a half (pass 0, 515) of the
+//   set-tiles take the four row tests, and the launch time fell there, not on the no-hit side (measured
+//   without the pad, HIP events, one job: 0 hits 2.917 -> 2.915 ms, 233 hits 2.971 -> 2.920, 515 hits
+//   3.049 -> 2.985; with it and against the parent in profiles/r13a).
+// Hit flush: a wave's full segment (kSeg = 128 entries) is flushed by that wave, blocking: one returning
+//   atomic per hit, s_waitcnt vmcnt(0), the stores (wave_flush_hits).  About 58 flushes per wave and
+//   launch at 233 hits per query.  Splitting the segment into halves whose atomics are issued at overflow
+//   and whose stores follow a tile later (the positions kept in a register meanwhile) measured level with
+//   the blocking flush or behind it, alone and with the check above; so did 192-entry segments
+//   (profiles/r13a/variants_explore.txt).
 // Ring protocol: ONE wait + work-group barrier per PAIR of tiles (it, it+1), it even; slot of tile t is
 // t mod 6; the tile at loop index j refills slot(j-2) with tile j+4 early in its MFMAs.
 //   Who issues a tile (loader half; widths with a multiple of four DMA pieces per tile: d = 128, 256,
@@ -1030,12 +1047,35 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   for (int s = 0; s < RD; ++s) af[s] = frag(0, s);
 
   int wcnt = 0;
-  auto append = [&](const f32x4& acc, float tau, int ql, uint32_t rowbase) {
-    const float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3])) - tau;
-    if (__ballot(mx >= 0.0f) == 0ull) return;
+  // one 16-query set's hits of one tile (header comment, "Hit check").  bound: the tile may be the shard's
+  // short last one -- only a block's last tile can be, and its epilogue is the one after the loop
+  auto append = [&](const f32x4& acc, float tau, int ql, uint32_t rowbase, auto bound) {
+    constexpr bool BOUND = decltype(bound)::value;
+    if constexpr (BOUND) {
+      const float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3])) - tau;
+      if (__ballot(mx >= 0.0f) == 0ull) return;
+    } else {
+      // v_max3 + v_max + v_cmp.  fmaxf first canonicalises two of the operands (v_max x, x), which an MFMA
+      // result never needs (it is no signalling NaN).  Only the prefilter: the row test below decides; a
+      // NaN tau (invalid query) fails it as it fails every row.
+      // The compiler pads no hazard of an asm statement, so the string opens with the pad for both MFMA
+      // hazards it can meet, whichever register mx gets (the counts are the compiler's own for this MFMA on
+      // gfx950: s_nop 7 before a VALU read of its result, s_nop 2 before a VALU write over its C operand):
+      //   mx may be given a register that the MFMA just ahead read as its C operand: 3 wait states, always;
+      //   the accumulators read here were written by the tile before: 8 wait states after its last MFMA.
+      //   This tile's 2 KS MFMAs lie between (each k-step is pinned by its sched_barrier, the statement is
+      //   volatile and follows them), which is 8 or more from d = 128 on; d = 64 has 4 and takes the long pad
+      //   (a long pad at every width measured 0.02 ms per launch at d = 768, profiles/r13a)
+      constexpr int kPad = 2 * KS >= 8 ? 2 : 7;
+      float mx;
+      asm volatile("s_nop %5\n\tv_max3_f32 %0, %1, %2, %3\n\tv_max_f32 %0, %0, %4"
+                   : "=&v"(mx)
+                   : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "n"(kPad));
+      if (__ballot(mx >= tau) == 0ull) return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bool hit = acc[j] >= tau && rowbase + j < nrows;
+      const bool hit = acc[j] >= tau && (!BOUND || rowbase + j < nrows);
       const uint64_t m = __ballot(hit);
       if (m == 0ull) continue;
       const int c = __builtin_popcountll(m);
@@ -1054,9 +1094,9 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
   };
 
   // (one ballot over both query sets' tiles measured slower: 2.95-2.97 vs 2.91 ms, profiles/r05y)
-  auto epilogue = [&](const f32x4& p0, const f32x4& p1, uint32_t rowbase) {
-    append(p0, tau0, r, rowbase);
-    append(p1, tau1, 16 + r, rowbase);
+  auto epilogue = [&](const f32x4& p0, const f32x4& p1, uint32_t rowbase, auto bound) {
+    append(p0, tau0, r, rowbase, bound);
+    append(p1, tau1, 16 + r, rowbase, bound);
   };
 
   int buf = 0;   // slot of tile it
@@ -1101,7 +1141,7 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
       if (s == KDMA && do_dma) issue(pslot, ntile);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (it > 0) epilogue(prev0, prev1, rb_prev);
+    if (it > 0) epilogue(prev0, prev1, rb_prev, std::false_type{});
     rb = (uint32_t)(tile * tmul + tph) * kT16 + 4 * kq;
     buf = nslot;
   };
@@ -1112,8 +1152,10 @@ __global__ __launch_bounds__(512, 1) void ip_scan32r_kernel(ScanArgs a) {
     iter(it, a0, a1, rbA, b0, b1, rbB);
     if (it + 1 < my_tiles) iter(it + 1, b0, b1, rbB, a0, a1, rbA);
   }
-  if (my_tiles & 1) epilogue(a0, a1, rbA);
-  else epilogue(b0, b1, rbB);
+  // the block's last tile: the only one that can be the shard's short tile, and its accumulators are fresh
+  // from the MFMAs: the compiler's own maximum (it pads the hazard) and the row bound
+  if (my_tiles & 1) epilogue(a0, a1, rbA, std::true_type{});
+  else epilogue(b0, b1, rbB, std::true_type{});
   if (wcnt) wave_flush_hits(a, qw, hk, hq, wcnt, lane);
 }
 
