@@ -141,7 +141,18 @@ _SIGNATURES = [
     ("drt_rmsnorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
     ("drt_attention_relbias_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     ("drt_gated_gelu_new_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
-    ("drt_t5_head_expand_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
+    ("drt_attention_relbias_train_fwd_bits_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32,
+                                                          c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
+    ("drt_attention_relbias_train_bwd_workspace", c_sz, [c_i64, c_i64, c_i32]),
+    ("drt_attention_relbias_train_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                                     c_i32, c_i32, c_f32, c_f32, c_u64, c_u64, c_vp, c_vp, c_sz,
+                                                     c_vp]),
+    ("drt_rmsnorm_bwd_workspace", c_sz, [c_i64, c_i32]),
+    ("drt_rmsnorm_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    ("drt_gated_gelu_new_bwd_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_u64, c_u64, c_vp, c_vp]),
+    ("drt_relu_bwd_bf16", c_i32, [c_vp, c_vp, c_i64, c_f32, c_u64, c_u64, c_vp, c_vp]),
+    ("drt_t5_embedding_bwd", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp]),
+    ("drt_t5_head_expand_bf16",c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     ("drt_t5_cross_pool_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
     ("drt_t5_head_reduce_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     ("drt_gemm_nt_f32", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),

@@ -770,7 +770,36 @@ int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void
 
 // The inference forward with a relative-position bias (T5Attention, modeling_t5.py: scores =
 // q k^T + position_bias, no 1 / sqrt(d) -- the caller passes scale = 1): relbias fp32
-// [heads][2 L - 1], entry (head, key - query + L - 1).  The RB instantiations of the kernel above.
+// [heads][2 L - 1], entry (head, key - query + L - 1).  The RB instantiations of the kernel above;
+// attention_relbias_launch serves it (drop = false) and the training forward below.
+static int attention_relbias_launch(const AttnArgs& a, bool drop, hipStream_t s) {
+  const int Lp = ((int)a.L + 31) & ~31;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (size_t)Lp * 8;
+  static bool attr_set = false;
+  if (!attr_set) {   // L > 224 stages more than the default 64 KiB (only the NB = 0 kernels get there)
+    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)attention_fwd_kernel<0, false, true>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)attention_fwd_kernel<0, true, true>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  const dim3 grid((unsigned)(a.B * a.heads));
+#define DRT_ARB_LAUNCH(NB_, NT_)                                                                          \
+  if (drop) hipLaunchKernelGGL((attention_fwd_kernel<NB_, true, true>), grid, dim3(NT_), lds, s, a);      \
+  else hipLaunchKernelGGL((attention_fwd_kernel<NB_, false, true>), grid, dim3(NT_), lds, s, a);          \
+  break;
+  switch (Lp / 32) {
+    case 1: DRT_ARB_LAUNCH(1, 256)
+    case 2: DRT_ARB_LAUNCH(2, 256)
+    case 3: DRT_ARB_LAUNCH(3, 256)
+    case 4: DRT_ARB_LAUNCH(4, 256)
+    case 5: DRT_ARB_LAUNCH(5, 320)
+    default: DRT_ARB_LAUNCH(0, 256)
+  }
+#undef DRT_ARB_LAUNCH
+  return hip_status(hipGetLastError());
+}
+
 int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx, int64_t B,
                                int64_t L, int32_t heads, int32_t head_dim, float scale, void* stream) {
   DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
@@ -778,25 +807,23 @@ int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float
   DRT_REQUIRE(qkv && ctx && relbias);
   AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, nullptr, 0.0f, 0, 0,
              nullptr, relbias};
-  const int Lp = ((int)L + 31) & ~31;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (size_t)Lp * 8;
-  static bool attr_set = false;
-  if (!attr_set) {   // L > 224 stages more than the default 64 KiB (only the NB = 0 kernel gets there)
-    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)attention_fwd_kernel<0, false, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  const dim3 grid((unsigned)(B * heads));
-  hipStream_t s = (hipStream_t)stream;
-  switch (Lp / 32) {
-    case 1: hipLaunchKernelGGL((attention_fwd_kernel<1, false, true>), grid, dim3(256), lds, s, a); break;
-    case 2: hipLaunchKernelGGL((attention_fwd_kernel<2, false, true>), grid, dim3(256), lds, s, a); break;
-    case 3: hipLaunchKernelGGL((attention_fwd_kernel<3, false, true>), grid, dim3(256), lds, s, a); break;
-    case 4: hipLaunchKernelGGL((attention_fwd_kernel<4, false, true>), grid, dim3(256), lds, s, a); break;
-    case 5: hipLaunchKernelGGL((attention_fwd_kernel<5, false, true>), grid, dim3(320), lds, s, a); break;
-    default: hipLaunchKernelGGL((attention_fwd_kernel<0, false, true>), grid, dim3(256), lds, s, a); break;
-  }
-  return hip_status(hipGetLastError());
+  return attention_relbias_launch(a, false, (hipStream_t)stream);
+}
+
+// The training forward of T5Attention: drt_attention_train_fwd_bits_bf16 (lse, attention-probability
+// dropout, keep bits) with the relative-position bias of drt_attention_relbias_bf16.  At drop_p = 0
+// the same kernels as drt_attention_relbias_bf16: the same ctx bits.
+int drt_attention_relbias_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx,
+                                              float* lse, uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads,
+                                              int32_t head_dim, float scale, float drop_p, uint64_t seed,
+                                              uint64_t site, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  if (B == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx && relbias);
+  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, lse, drop_p, seed, site,
+             drop_bits, relbias};
+  return attention_relbias_launch(a, drop_p > 0.0f, (hipStream_t)stream);
 }
 
 int drt_pool_bf16(const void* hidden, const int64_t* mask, int64_t B, int64_t L, int32_t H, int32_t mode,

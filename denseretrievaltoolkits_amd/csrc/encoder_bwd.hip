@@ -293,6 +293,9 @@ struct AttnBwdArgs {
   const uint32_t* drop_bits;  // optional keep bits written by the forward ([B][heads][L][ceil(L/32)]);
                               // NULL: the same bits drawn again from the hash
   float* dsum;                // optional [B][3H] (L > 160: [B][ceil(L / 128)][3H]): column sums of dQKV
+  const float* relbias;       // RB kernels: [heads][2L-1] fp32, the forward's relative-position bias
+  float* dtab;                // RB kernels: [B][heads][2L-1] (L > 160: [B][ceil(L / 128)][heads][2L-1]) fp32,
+                              // each work-group's sums of dS along the diagonals k - q
 };
 
 __device__ __forceinline__ int ab_rc(int row, int chunk) { return row * kAbRow + ((chunk ^ ((row >> 1) & 7)) << 4); }
@@ -341,15 +344,18 @@ __device__ __forceinline__ bf16x8 ab_tr8o(const char* img, int off0, int off1) {
 //   P2 (lane = query, 4 keys e0..e0+3):  P = exp2(S log2e + (kb2 - lse2)),   dS = P (keep dP / (1-p) - Dv)
 // Same roundings as the per-element form: fma(S, log2e, kbias - lse2) vs fma(S, log2e, kbias) - lse2 can
 // differ in the last bit of the exponent argument (checked against torch fp32, not bitwise).
-template <bool DROP>
+// RB: rbv = the relative-position biases (x log2e) of this lane's key and the four queries; they join
+// the key bias before lse2 leaves and before the fma, as in the forward (kb + rb, then fma(S, log2e, .)).
+template <bool DROP, bool RB = false>
 __device__ __forceinline__ void ab_p1_pairs(const f32x16& sv, const f32x16& dp, int e0, const f32x4& lq,
                                             const f32x4& dq, float kbias, const u32x4& wk, uint32_t lanebit,
-                                            float inv, bf16x8 (&pa)[2], bf16x8 (&sa)[2]) {
+                                            float inv, bf16x8 (&pa)[2], bf16x8 (&sa)[2],
+                                            const f32x4& rbv = f32x4{}) {
   const f32x2 l2e = {kLog2e, kLog2e}, kb = {kbias, kbias}, iv = {inv, inv};
 #pragma unroll
   for (int u = 0; u < 4; u += 2) {
     const int e = e0 + u;
-    const f32x2 c = kb - f32x2{lq[u], lq[u + 1]};
+    const f32x2 c = (RB ? kb + f32x2{rbv[u], rbv[u + 1]} : kb) - f32x2{lq[u], lq[u + 1]};
     f32x2 x = __builtin_elementwise_fma(f32x2{sv[e], sv[e + 1]}, l2e, c);
     f32x2 p = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
     f32x2 ds, pd = p;
@@ -369,9 +375,11 @@ __device__ __forceinline__ void ab_p1_pairs(const f32x16& sv, const f32x16& dp, 
 }
 
 // wbits: bit u (u < 4) = keep of key e0 + u's pair element for this lane's query
-template <bool DROP>
+// DSF: also hand back the four fp32 dS (before the bf16 rounding) -- the relative-bias gradient
+template <bool DROP, bool DSF = false>
 __device__ __forceinline__ void ab_p2_pairs(const f32x16& st, const f32x16& dpt, int e0, const f32x4& kbv, float lq,
-                                            float dq, uint32_t wbits, float inv, bf16x8 (&sa)[2]) {
+                                            float dq, uint32_t wbits, float inv, bf16x8 (&sa)[2],
+                                            f32x4* dsf = nullptr) {
   const f32x2 l2e = {kLog2e, kLog2e}, lq2 = {lq, lq}, nd = {-dq, -dq}, iv = {inv, inv};
 #pragma unroll
   for (int u = 0; u < 4; u += 2) {
@@ -386,6 +394,10 @@ __device__ __forceinline__ void ab_p2_pairs(const f32x16& st, const f32x16& dpt,
     } else {
       ds = p * (f32x2{dpt[e], dpt[e + 1]} + nd);
     }
+    if (DSF) {
+      (*dsf)[u] = ds[0];
+      (*dsf)[u + 1] = ds[1];
+    }
     sa[e >> 3][e & 7] = (__bf16)ds[0];
     sa[e >> 3][(e & 7) + 1] = (__bf16)ds[1];
   }
@@ -396,7 +408,22 @@ __device__ __forceinline__ void ab_p2_pairs(const f32x16& st, const f32x16& dpt,
 // staging (one fma + one sub + v_exp per score); the dropout scale 1 / (1 - p) leaves the
 // per-element path: dS = P (keep ? dP : 0) / (1 - p) - P Dv is one fma on the kept dP, and
 // dV = (1 / (1 - p)) sum_q (keep P)^T dO scales the accumulator once at the store.
-template <int NB, bool DROP>
+// RB (T5Attention: S = Qs K^T + table[head][k - q + L - 1] + key bias): the head's biases sit in LDS
+// (x log2e, as the forward holds them) at rbs[k - q + Lp - 1], zero outside the table, and join the key
+// bias exactly where the forward adds them, so an all-zero table leaves every bit of the !RB kernel's
+// dQKV.  Phase 1 (lane = key, four consecutive queries per step) needs them in DESCENDING table order
+// at an offset that is aligned to nothing; it reads them as one aligned 16-B vector from rbq, four
+// copies of the reversed table shifted by 0..3 entries (copy c, entry t = reversed entry t + c): a
+// lane's copy (Lp - 1 - key) & 3 and base are fixed, the query block adds an immediate.  (Four 4-B
+// reads per step, which the compiler paired into ds_read2_b32, gave run-to-run different dK / dV in
+// the 8-wave NB = 5 instance on an MI355X; the cause was not found at the ISA level, the aligned
+// reads are bit-reproducible and cheaper.)  Their gradient dtable[d] = sum over (q, k < L, k - q = d) of dS is summed in phase 2 (lane =
+// query, 16 keys of a tile in registers) from the fp32 dS, before its bf16 rounding, with LDS float
+// atomics into dts[k - q + Lp - 1] (the 32 queries of a half-wave hit consecutive banks); padding
+// queries and keys add nothing.  The work-group's 2L-1 sums go to a.dtab[sequence][head]; the host
+// sums the sequences in a fixed order.  (The LDS atomics of the query blocks of one work-group land
+// in hardware order: dtable is deterministic across sequences, not bit-reproducible within one.)
+template <int NB, bool DROP, bool RB = false>
 __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void attention_bwd_rk_kernel(AttnBwdArgs a) {
   constexpr int NW = NB == 5 ? 8 : 4;
   constexpr int NT = NW * 64;
@@ -411,6 +438,9 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
   float* dv = lse2 + Lp;                             // [Lp]  Dv
   float* kb2 = dv + Lp;                              // [Lp]  key bias (0 / -FLT_MAX)
   uint32_t* kbits = (uint32_t*)(kb2 + Lp);           // [NB][Lp] keep words (DROP)
+  float* rbs = (float*)(kbits + (DROP ? NB * Lp : 0));   // [2 Lp] relative biases * log2e (RB)
+  float* dts = rbs + 2 * Lp;                         // [2 Lp] their gradient (RB)
+  float* rbq = dts + 2 * Lp;                         // [4][2 Lp + 4] shifted reversed copies of rbs (RB)
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
@@ -520,6 +550,19 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
         kbits[kbi * Lp + qq] = qq < L ? w : 0u;
       }
     }
+    if (RB) {
+      const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
+      for (int i = tid; i < 2 * Lp; i += NT) {
+        const int j = i - (Lp - L);                  // table entry k - q + L - 1
+        rbs[i] = (j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+        dts[i] = 0.0f;
+      }
+      for (int i = tid; i < 4 * 2 * Lp; i += NT) {   // rbq[c][t] = rbs[2 Lp - 2 - (t + c)]
+        const int c = i / (2 * Lp), t = i - c * 2 * Lp;
+        const int ii = 2 * Lp - 2 - (t + c), j = ii - (Lp - L);
+        rbq[c * (2 * Lp + 4) + t] = (ii >= 0 && j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+      }
+    }
   }
   __syncthreads();
 
@@ -558,6 +601,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       vf[k4] = *(const bf16x8*)(Vs + blk * 4096 + off.offA[k4]);
     }
     const float kbias = kb2[key];
+    const float* rbq1 = rbq + ((Lp - 1 - key) & 3) * (2 * Lp + 4) + ((Lp - 1 - key) & ~3);   // RB
     f32x16 dK[2], dV[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -590,7 +634,10 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
         const f32x4 dq = *(const f32x4*)(dv + q0);
         u32x4 wk = {};
         if (DROP) wk = *(const u32x4*)(kbits + blk * Lp + q0);
-        ab_p1_pairs<DROP>(sv, dp, 4 * g, lq, dq, kbias, wk, lanebit, inv, pa, sa);
+        f32x4 rbv = {};
+        // rbs[key + Lp - 1 - (q0 + u)], u = 0..3: reversed entries (Lp - 1 - key) + q0 + u
+        if (RB) rbv = *(const f32x4*)(rbq1 + q0);
+        ab_p1_pairs<DROP, RB>(sv, dp, 4 * g, lq, dq, kbias, wk, lanebit, inv, pa, sa, rbv);
       }
       // dV += Pd^T dO, dK += dS^T Qs over the block's 32 queries (2 k-steps of 16, permuted rows)
 #pragma unroll
@@ -650,8 +697,20 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       bf16x8 sa[2];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const f32x4 kbv = *(const f32x4*)(kb2 + kbk * 32 + 8 * g + 4 * h);
-        ab_p2_pairs<DROP>(st, dpt, 4 * g, kbv, lq, dq, wq >> (8 * g), inv, sa);
+        f32x4 kbv = *(const f32x4*)(kb2 + kbk * 32 + 8 * g + 4 * h);
+        f32x4 dsf;
+        const int k0 = kbk * 32 + 8 * g + 4 * h;    // this lane's four keys k0 .. k0 + 3
+        if (RB) {
+          const float* rp = rbs + (Lp - 1 - q) + k0;
+          kbv += f32x4{rp[0], rp[1], rp[2], rp[3]};
+        }
+        ab_p2_pairs<DROP, RB>(st, dpt, 4 * g, kbv, lq, dq, wq >> (8 * g), inv, sa, &dsf);
+        if (RB && q < L) {
+          float* dp2 = dts + (Lp - 1 - q) + k0;
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (k0 + u < L) __hip_atomic_fetch_add(dp2 + u, dsf[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -715,6 +774,10 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       *(bf16x8*)(a.dqkv + (row0 + row) * ld + m * a.H + hd * 64 + c * 8) = *(const bf16x8*)(img + ab_rc(row, c));
     }
   }
+  if (RB) {   // this (sequence, head)'s diagonal sums (complete since the barrier after the phases)
+    float* dst = a.dtab + ((int64_t)b * a.heads + hd) * (2 * L - 1);
+    for (int i = tid; i < 2 * L - 1; i += NT) dst[i] = dts[i + Lp - L];
+  }
   if (a.dsum && tid < 192) {   // the blocks' column sums in block order -> dsum[b][3H]
     const int m = tid >> 6, col = tid & 63;
     float t = 0.f;
@@ -742,8 +805,39 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
 constexpr int kAblMaxSeq = 512;
 constexpr int kAblGroup = 128;   // rows per work-group (4 waves x 32)
 
-template <bool DROP>
+// RB: the head's whole bias table (x log2e) in LDS at rbs[k - q + 511] (q, k < 512), zero outside
+// the table (the dkdv kernel: its shifted reversed copies); the dq kernel also sums dS along the diagonals into dts (as attention_bwd_rk_kernel) and
+// writes its group's 2L-1 sums -- zero where its 128 queries have no entry -- to
+// a.dtab[sequence][group][head].
+constexpr int kAblRb = 2 * kAblMaxSeq;
+
+template <bool RB>
+__device__ __forceinline__ void abl_stage_relbias(const AttnBwdArgs& a, int hd, int L, float* rbs, float* dts) {
+  if (!RB) return;
+  const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
+  for (int i = threadIdx.x; i < kAblRb; i += 256) {
+    const int j = i - (kAblMaxSeq - L);              // table entry k - q + L - 1
+    rbs[i] = (j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+    dts[i] = 0.0f;
+  }
+}
+// The dkdv kernel's image: four copies of the reversed table shifted by 0..3 entries, as
+// attention_bwd_rk_kernel's rbq (one aligned 16-B read per four queries).
+constexpr int kAblRbq = kAblRb + 4;
+template <bool RB>
+__device__ __forceinline__ void abl_stage_relbias_rev(const AttnBwdArgs& a, int hd, int L, float* rbq) {
+  if (!RB) return;
+  const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
+  for (int i = threadIdx.x; i < 4 * kAblRb; i += 256) {
+    const int c = i / kAblRb, t = i - c * kAblRb;
+    const int ii = kAblRb - 2 - (t + c), j = ii - (kAblMaxSeq - L);
+    rbq[c * kAblRbq + t] = (ii >= 0 && j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+  }
+}
+
+template <bool DROP, bool RB = false>
 __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float rbq[RB ? 4 * kAblRbq : 4];
   __shared__ __attribute__((aligned(16))) char Qs[32 * kAbRow];
   __shared__ __attribute__((aligned(16))) char Os[32 * kAbRow];
   __shared__ __attribute__((aligned(16))) float lse2[32];
@@ -832,6 +926,8 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
       dK[t][e] = 0.f;
       dV[t][e] = 0.f;
     }
+  abl_stage_relbias_rev<RB>(a, hd, L, rbq);         // visible after the loop's first barrier
+  const float* rbq1 = rbq + (RB ? ((kAblMaxSeq - 1 - key) & 3) * kAblRbq + ((kAblMaxSeq - 1 - key) & ~3) : 0);
   load(0);
   for (int qb = 0; qb < nqb; ++qb) {
     store(qb);
@@ -859,7 +955,9 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
         const f32x4 dq = *(const f32x4*)(dvs + q0);
         u32x4 wk = {};
         if (DROP) wk = *(const u32x4*)(&kw[wave][q0]);
-        ab_p1_pairs<DROP>(sv, dp, 4 * g, lq, dq, kbias, wk, lanebit, inv, pa, sa);
+        f32x4 rbv = {};
+        if (RB) rbv = *(const f32x4*)(rbq1 + qb * 32 + q0);
+        ab_p1_pairs<DROP, RB>(sv, dp, 4 * g, lq, dq, kbias, wk, lanebit, inv, pa, sa, rbv);
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -912,8 +1010,10 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
   }
 }
 
-template <bool DROP>
+template <bool DROP, bool RB = false>
 __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdArgs a) {
+  __shared__ float rbs[RB ? kAblRb : 1];
+  __shared__ float dts[RB ? kAblRb : 1];
   __shared__ __attribute__((aligned(16))) char Ks[32 * kAbRow];
   __shared__ __attribute__((aligned(16))) char Vs[32 * kAbRow];
   __shared__ __attribute__((aligned(16))) float kb2[32];
@@ -987,6 +1087,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) dQ[t][e] = 0.f;
+  abl_stage_relbias<RB>(a, hd, L, rbs, dts);        // visible after the loop's first barrier
   load(0);
   for (int kb = 0; kb < nkb; ++kb) {
     store();
@@ -1010,8 +1111,20 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
       bf16x8 sa[2];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const f32x4 kbv = *(const f32x4*)(kb2 + 8 * g + 4 * h);
-        ab_p2_pairs<DROP>(st, dpt, 4 * g, kbv, lq, dq, wq0 >> (8 * g), inv, sa);
+        f32x4 kbv = *(const f32x4*)(kb2 + 8 * g + 4 * h);
+        f32x4 dsf;
+        const int k0 = kb * 32 + 8 * g + 4 * h;      // this lane's four keys k0 .. k0 + 3
+        if (RB) {
+          const float* rp = rbs + (kAblMaxSeq - 1 - q) + k0;
+          kbv += f32x4{rp[0], rp[1], rp[2], rp[3]};
+        }
+        ab_p2_pairs<DROP, RB>(st, dpt, 4 * g, kbv, lq, dq, wq0 >> (8 * g), inv, sa, &dsf);
+        if (RB && q < L) {
+          float* dp2 = dts + (kAblMaxSeq - 1 - q) + k0;
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (k0 + u < L) __hip_atomic_fetch_add(dp2 + u, dsf[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -1042,6 +1155,11 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
   for (int i = tid; i < kAblGroup * 8; i += 256) {
     const int row = i >> 3, c = i & 7, qq = grp * kAblGroup + row;
     if (qq < L) *(bf16x8*)(a.dqkv + (row0 + qq) * ld + hd * 64 + c * 8) = *(const bf16x8*)(Out + ab_rc(row, c));
+  }
+  if (RB) {   // complete since the loop's last barrier
+    const int G = (L + kAblGroup - 1) / kAblGroup;
+    float* dst = a.dtab + (((int64_t)b * G + grp) * a.heads + hd) * (2 * L - 1);
+    for (int i = tid; i < 2 * L - 1; i += 256) dst[i] = dts[i + kAblMaxSeq - L];
   }
   if (a.dsum && tid < 64) {
     const int G = (L + kAblGroup - 1) / kAblGroup;
@@ -1254,7 +1372,8 @@ int drt_attention_train_bwd_bf16(const void* qkv, const void* ctx, const void* d
 static int attention_bwd_launch(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                 const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
                                 int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                uint64_t site, float* dsum_part, void* stream);
+                                uint64_t site, float* dsum_part, void* stream, const float* relbias = nullptr,
+                                float* dtab_part = nullptr);
 
 int drt_attention_train_bwd_bits_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                       const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
@@ -1290,22 +1409,60 @@ int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const vo
   return colsum_launch<float>(part, rows, n, dbias, part + (size_t)B * gmax * n, (hipStream_t)stream);
 }
 
+// Work-group rows of the relative-bias gradient: one per sequence (L <= 160) or per (sequence,
+// 128-query group), each [heads][2L-1] fp32; then the column sum's own scratch.
+static int64_t relbias_bwd_rows(int64_t B, int64_t L) {
+  return L > kAbMaxSeq ? B * ((L + kAblGroup - 1) / kAblGroup) : B;
+}
+size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads) {
+  if (B <= 0 || L <= 0 || L > kAblMaxSeq || heads <= 0) return 0;
+  const int64_t n = (int64_t)heads * (2 * L - 1), rows = relbias_bwd_rows(B, L);
+  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
+}
+
+// T5Attention backward: drt_attention_train_bwd_bits_bf16 with the forward's relative-position bias
+// relbias fp32 [heads][2L-1] in the score rebuild, also writing its gradient dtable [heads][2L-1]:
+// the work-groups' diagonal sums of the fp32 dS (in ws), summed over the sequences in a fixed order.
+int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                         const int64_t* mask, const float* relbias, const uint32_t* drop_bits,
+                                         void* dqkv, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
+                                         float scale, float drop_p, uint64_t seed, uint64_t site, float* dtable,
+                                         void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(B > 0 && L > 0 && L <= kAblMaxSeq && heads > 0 && relbias && dtable && ws);
+  DRT_REQUIRE(ws_bytes >= drt_attention_relbias_train_bwd_workspace(B, L, heads));
+  float* part = (float*)ws;
+  const int rc = attention_bwd_launch(qkv, ctx, dctx, lse, mask, drop_bits, dqkv, B, L, heads, head_dim, scale,
+                                      drop_p, seed, site, nullptr, stream, relbias, part);
+  if (rc) return rc;
+  const int64_t n = (int64_t)heads * (2 * L - 1), rows = relbias_bwd_rows(B, L);
+  return colsum_launch<float>(part, rows, n, dtable, part + (size_t)rows * n, (hipStream_t)stream);
+}
+
 static int attention_bwd_launch(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                 const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
                                 int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                uint64_t site, float* dsum_part, void* stream) {
+                                uint64_t site, float* dsum_part, void* stream, const float* relbias,
+                                float* dtab_part) {
   DRT_REQUIRE(B >= 0 && L > 0 && L <= kAblMaxSeq && heads > 0 && head_dim == 64);
+  DRT_REQUIRE(!relbias == !dtab_part);
   DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
   if (B == 0) return DRT_OK;
   DRT_REQUIRE(qkv && ctx && dctx && lse && dqkv);
   AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, mask, (__bf16*)dqkv, B, L,
-                heads, heads * 64, scale, drop_p, seed, site, drop_bits, dsum_part};
+                heads, heads * 64, scale, drop_p, seed, site, drop_bits, dsum_part, relbias, dtab_part};
+  const bool rb = relbias != nullptr;
   if (L > kAbMaxSeq) {   // streamed kernels: dK / dV over key groups, dQ over query groups
     const bool drop = drop_p > 0.0f;
     DRT_REQUIRE(!drop || drop_bits);   // the forward's keep bits (drt_attention_train_fwd_bits_bf16)
     const dim3 grid((unsigned)(B * heads), (unsigned)((L + kAblGroup - 1) / kAblGroup));
     hipStream_t st = (hipStream_t)stream;
-    if (drop) {
+    if (rb && drop) {
+      hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<true, true>), grid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attention_bwd_long_dq_kernel<true, true>), grid, dim3(256), 0, st, a);
+    } else if (rb) {
+      hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<false, true>), grid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attention_bwd_long_dq_kernel<false, true>), grid, dim3(256), 0, st, a);
+    } else if (drop) {
       hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<true>), grid, dim3(256), 0, st, a);
       hipLaunchKernelGGL((attention_bwd_long_dq_kernel<true>), grid, dim3(256), 0, st, a);
     } else {
@@ -1319,12 +1476,18 @@ static int attention_bwd_launch(const void* qkv, const void* ctx, const void* dc
   const dim3 grid((unsigned)(B * heads));
   const bool drop = drop_p > 0.0f;
   // register-resident P / dS; dropout from the forward's keep bits (or the same bits drawn again)
-  size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + (drop ? (size_t)nb * Lp * 4 : 0);
+  size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + (drop ? (size_t)nb * Lp * 4 : 0) +
+               (rb ? (size_t)4 * Lp * 4 + (size_t)4 * (2 * Lp + 4) * 4 : 0);   // RB: the bias diagonals and their
+                                                // gradient, 2 Lp floats each, + 4 shifted reversed copies
   DRT_REQUIRE(lds <= 160 * 1024);
   static bool rk_attr = false;
   if (!rk_attr) {
     const void* ks[] = {(const void*)attention_bwd_rk_kernel<4, false>, (const void*)attention_bwd_rk_kernel<4, true>,
-                        (const void*)attention_bwd_rk_kernel<5, false>, (const void*)attention_bwd_rk_kernel<5, true>};
+                        (const void*)attention_bwd_rk_kernel<5, false>, (const void*)attention_bwd_rk_kernel<5, true>,
+                        (const void*)attention_bwd_rk_kernel<4, false, true>,
+                        (const void*)attention_bwd_rk_kernel<4, true, true>,
+                        (const void*)attention_bwd_rk_kernel<5, false, true>,
+                        (const void*)attention_bwd_rk_kernel<5, true, true>};
     for (const void* f : ks) DRT_CHECK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     rk_attr = true;
   }
@@ -1332,7 +1495,9 @@ static int attention_bwd_launch(const void* qkv, const void* ctx, const void* dc
   const dim3 blk(nb == 5 ? 512 : 256);
 #define DRT_AB_LAUNCH(NB_)                                                                              \
   case NB_:                                                                                             \
-    if (drop) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, true>), grid, blk, lds, st, a);         \
+    if (rb && drop) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, true, true>), grid, blk, lds, st, a);  \
+    else if (rb) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, false, true>), grid, blk, lds, st, a);    \
+    else if (drop) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, true>), grid, blk, lds, st, a);    \
     else hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, false>), grid, blk, lds, st, a);             \
     break;
   switch (nb) {

@@ -9,13 +9,17 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   kernels (model/encoder.HipBertEncoder): bf16 MFMA GEMMs, fused attention, fp32
   LayerNorm statistics, pooling / head / L2-normalise kernels.  ``hidden`` is
   returned in bf16, ``reps`` in fp32.  ``encoder_only`` T5 towers (T5EncoderModel)
-  take the same path through model/t5_encoder.HipT5Encoder; with autograd they
-  stay on the HF module.
+  take the same path through model/t5_encoder.HipT5Encoder.
 * encode with autograd (training, or eval mode with grad on, where the reference
   returns differentiable reps) runs BERT towers up to L = 512 on the HIP training
   tower (model/train_tower.py: forward with saved bf16 activations + backward on
   HIP kernels, HF train-mode dropout regenerated from a counter hash; dropout is
-  off in eval mode); other towers stay on the HF module under autograd.
+  off in eval mode).  ``encoder_only`` T5 towers stay on the HF module under
+  autograd by default; with ``hip_train_t5 = True`` (attribute, or
+  ``model_args.hip_train_t5``) a supported T5EncoderModel on the GPU runs the HIP
+  T5 training tower (model/t5_train_tower.py: RMSNorm / ReLU / gated-GELU /
+  relative-bias attention backwards, fp32 gradients for every HF parameter).
+  Other towers, and the T5 reranker's decoder, stay on the HF module under autograd.
 * the training score matrix + cross entropy (forward :107-119) runs on the
   fused fp32 kernels with autograd (torch.ops.drt.score_ce_fwd, score_ce.py); with
   ``forward(..., teacher_scores=)`` the distillation loss of torch.ops.drt.score_kd_fwd.
@@ -40,6 +44,7 @@ from transformers.modeling_outputs import ModelOutput
 from .encoder import HipBertEncoder, l2_normalize_, linear_head
 from .t5_encoder import HipT5Encoder, t5_supported
 from .train_tower import MAX_TRAIN_SEQ, tower_supported, train_hidden
+from .t5_train_tower import t5_tower_supported, train_hidden_t5
 from .linear import LinearHead
 
 logger = logging.getLogger(__name__)
@@ -89,6 +94,8 @@ class DRModel(nn.Module):
         self.feature = feature
         self.pooling = pooling
         self.hip_train = True   # HIP training tower for BERT towers with L <= 512 (set False: HF autograd)
+        # opt-in: T5EncoderModel towers with autograd on the HIP T5 training tower (default: HF module)
+        self.hip_train_t5 = bool(getattr(model_args, "hip_train_t5", False))
         self.normalize = normalize
         self.model_args = model_args
         self.train_args = train_args
@@ -213,10 +220,18 @@ class DRModel(nn.Module):
             return hidden, reps
         # forward with autograd: BERT towers up to MAX_TRAIN_SEQ tokens run the HIP training tower
         # (saved bf16 activations + backward on HIP kernels, HF dropout semantics in train mode,
-        # model/train_tower.py); anything else keeps the HF module under autograd.
+        # model/train_tower.py), T5EncoderModel towers the T5 one when hip_train_t5 is set
+        # (model/t5_train_tower.py); anything else keeps the HF module under autograd.
         why = None
+        is_t5 = type(model).__name__ == "T5EncoderModel"
         if self.feature != "last_hidden_state":
             why = f"feature {self.feature!r}"
+        elif is_t5 and not self.hip_train_t5:
+            why = "T5 tower with hip_train_t5 = False"
+        elif is_t5 and not next(model.parameters()).is_cuda:
+            why = "tower on the CPU"
+        elif is_t5:
+            why = t5_tower_supported(model, items["input_ids"].shape[1])
         elif not self.hip_train:
             why = "hip_train = False"
         elif not next(model.parameters()).is_cuda:
@@ -225,7 +240,9 @@ class DRModel(nn.Module):
             why = f"sequence length {items['input_ids'].shape[1]} > {MAX_TRAIN_SEQ}"
         else:
             why = tower_supported(model)
-        if why is None:
+        if why is None and is_t5:
+            hidden = train_hidden_t5(model, items["input_ids"], items.get("attention_mask"))
+        elif why is None:
             hidden = train_hidden(model, items["input_ids"], items.get("attention_mask"),
                                   token_type_ids=items.get("token_type_ids"))
         else:

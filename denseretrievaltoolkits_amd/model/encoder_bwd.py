@@ -54,8 +54,8 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 
 def linear_backward(dy: torch.Tensor, x: torch.Tensor, w_t: torch.Tensor, want_dx: bool = True,
                     resid: Optional[torch.Tensor] = None, gelu_pre: Optional[torch.Tensor] = None,
-                    db: Optional[torch.Tensor] = None, dx_colsum: Optional[torch.Tensor] = None
-                    ) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+                    db: Optional[torch.Tensor] = None, dx_colsum: Optional[torch.Tensor] = None,
+                    want_db: bool = True) -> Tuple[Optional[torch.Tensor], torch.Tensor, Optional[torch.Tensor]]:
     """Gradients of y = x W^T + b (nn.Linear, W [N, K]) for dy [T, N], x [T, K] (bf16 CUDA),
     given w_t = W^T [K, N] bf16.  Returns (dx bf16 [T, K] or None, dW fp32 [N, K], db fp32 [N]);
     ``resid`` [T, K] bf16 is added to dx in the dgrad GEMM's epilogue (a residual branch);
@@ -64,7 +64,7 @@ def linear_backward(dy: torch.Tensor, x: torch.Tensor, w_t: torch.Tensor, want_d
     produced by dy's producer (the LayerNorm / attention backward), returned as is instead of a
     column-sum pass over dy.  ``dx_colsum`` [K] fp32 (with ``gelu_pre``): also filled with the column
     sums of dx -- the bias gradient of the GELU's linear -- from the dgrad GEMM's epilogue
-    (drt_linear_dgelu_bias_bf16)."""
+    (drt_linear_dgelu_bias_bf16).  ``want_db`` False (a linear without a bias): db is None."""
     lib = _native.load()
     dev = dy.device
     s = _native.stream_ptr(dev)
@@ -95,6 +95,8 @@ def linear_backward(dy: torch.Tensor, x: torch.Tensor, w_t: torch.Tensor, want_d
             _native.check(lib.drt_linear_bf16_ws(dy.data_ptr(), w_t.data_ptr(), None, _ptr(resid), dx.data_ptr(), T, K,
                                                  N, 0, _ptr(ws), nb, s), "dgrad")
     dW = wgrad(dy, x)
+    if not want_db:
+        return dx, dW, None
     return dx, dW, (db if db is not None else colsum(dy))
 
 

@@ -557,6 +557,53 @@ int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float
                                int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
                                void* stream);
 int drt_gated_gelu_new_bf16(const void* X, int64_t M, int64_t F, void* out, void* stream);
+/* T5 encoder training (HF T5EncoderModel under autograd): the attention forward / backward with the
+ * relative-position bias, and the backwards of T5LayerNorm, the two feed-forward activations and
+ * the shared embedding.  The projections use drt_linear_bf16* / drt_linear_wgrad_bf16.
+ * drt_attention_relbias_train_fwd_bits_bf16: drt_attention_train_fwd_bits_bf16 (lse, attention-
+ *   probability dropout, keep bits) with relbias as drt_attention_relbias_bf16 takes it; at
+ *   drop_p = 0 ctx has drt_attention_relbias_bf16's bits.
+ * drt_attention_relbias_train_bwd_bf16: drt_attention_train_bwd_bits_bf16 with that bias in the
+ *   score rebuild (S = Qs K^T + relbias[h][k - q + L - 1] + key bias), also writing its gradient
+ *   dtable fp32 [heads][2L-1]: dtable[h][d + L - 1] = sum over sequences and (q, k < L, k - q = d)
+ *   of dS, taken from the fp32 dS before its bf16 rounding; padding rows and keys add nothing, a
+ *   masked key adds an exact 0.  Each work-group sums its diagonals with LDS float atomics and
+ *   leaves them in ws (drt_attention_relbias_train_bwd_workspace bytes); the sum over work-groups
+ *   runs in a fixed order.  So dtable is reproducible up to the order of the LDS atomics inside one
+ *   (sequence, head); dqkv is bit-reproducible, and with an all-zero relbias it has
+ *   drt_attention_train_bwd_bits_bf16's bits.  L <= 512 (L > 160 with dropout needs drop_bits).
+ * drt_rmsnorm_bwd_bf16: for y = x r gamma, r = rsqrt(mean x^2 + eps) over bf16 x [M, H]:
+ *   dx = gamma dy r - x r^3 mean(gamma dy x) (+ dres, a residual gradient, may be NULL), bf16;
+ *   dgamma fp32 [H] = sum_rows dy x r from per-block partials summed in a fixed order
+ *   (deterministic).  fp32 statistics; H % 256 == 0, H <= 1024; ws: drt_rmsnorm_bwd_workspace.
+ * drt_gated_gelu_new_bwd_bf16: from dy [M, F] and the saved pre-activations X = (a | b) [M, 2F] of
+ *   f = gelu_new(a) b: dX [M, 2F] = (dy b gelu_new'(a) | dy gelu_new(a)).
+ * drt_relu_bwd_bf16: dx = dy (f > 0) from the saved output f = relu(pre); n % 8 == 0.
+ *   Both first drop dy with drt_dropout_add_bf16's mask of (drop_p, seed, site) over the [M, F]
+ *   index (HF drops f before wo); drop_p = 0: none.  Pointers 16-byte aligned.
+ * drt_t5_embedding_bwd: dshared[ids[t]] += d[t] over bf16 d [B*L, H] into fp32 dshared [vocab, H]
+ *   (the caller zeroes it; fp32 atomics; no position / type table, no padding row).           */
+int drt_attention_relbias_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, const float* relbias,
+                                              void* ctx, float* lse, uint32_t* drop_bits, int64_t B,
+                                              int64_t L, int32_t heads, int32_t head_dim, float scale,
+                                              float drop_p, uint64_t seed, uint64_t site, void* stream);
+size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads);
+int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx,
+                                         const float* lse, const int64_t* mask, const float* relbias,
+                                         const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
+                                         int32_t heads, int32_t head_dim, float scale, float drop_p,
+                                         uint64_t seed, uint64_t site, float* dtable, void* ws,
+                                         size_t ws_bytes, void* stream);
+size_t drt_rmsnorm_bwd_workspace(int64_t M, int32_t H);
+int drt_rmsnorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M,
+                         int32_t H, const void* dres, void* dx, float* dgamma, void* ws,
+                         size_t ws_bytes, void* stream);
+int drt_gated_gelu_new_bwd_bf16(const void* dy, const void* X, int64_t M, int64_t F, float drop_p,
+                                uint64_t seed, uint64_t site, void* dX, void* stream);
+int drt_relu_bwd_bf16(const void* dy, const void* f, int64_t n, float drop_p, uint64_t seed,
+                      uint64_t site, void* dx, void* stream);
+int drt_t5_embedding_bwd(const int64_t* ids, const void* d, int64_t B, int64_t L, int32_t H,
+                         int64_t vocab, float* dshared, void* stream);
 /* One-step T5 decoder (T5ForConditionalGeneration with a single decoder token: monoT5 rerankers).
  * With one query per sequence the cross-attention runs in absorbed form over the encoder output
  * enc [B, L, D] bf16 itself; no K / V projection of it is formed.  Wk, Wv: EncDecAttention.k / .v
