@@ -96,8 +96,6 @@ _SIGNATURES = [
     ("drt_layernorm_f32_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
     ("drt_attention_fwd_lse_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     ("drt_layernorm_bwd_workspace", c_sz, [c_i64, c_i32]),
-    ("drt_layernorm_bwd_drop_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_f32, c_u64,
-                                            c_u64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("drt_layernorm_bwd_sum_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_f32, c_u64,
                                            c_u64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("drt_linear_bf16_ex", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_u64,
@@ -117,13 +115,7 @@ _SIGNATURES = [
     ("drt_embed_ln_pre", c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp,
                                  c_vp]),
     ("drt_gelu_bf16", c_i32, [c_vp, c_i64, c_vp, c_vp]),
-    ("drt_embedding_bwd", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    ("drt_embedding_bwd_types", c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp,
-                                         c_vp]),
-    ("drt_attention_train_fwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_f32,
-                                             ctypes.c_uint64, ctypes.c_uint64, c_vp]),
-    ("drt_attention_train_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32,
-                                             c_f32, ctypes.c_uint64, ctypes.c_uint64, c_vp]),
+    ("drt_embedding_bwd", c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     ("drt_dropout_add_bf16", c_i32, [c_vp, c_vp, c_i64, c_f32, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp]),
     ("drt_attention_train_fwd_bits_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32,
                                                   c_f32, c_u64, c_u64, c_vp]),

@@ -579,15 +579,51 @@ __global__ __launch_bounds__(256) void l2norm_kernel(float* x, int64_t B, int H,
   }
 }
 
+// The host driver behind the five attention forward entries: every instantiation of
+// attention_fwd_kernel.  rb (the relbias entries; T5Attention, modeling_t5.py: scores = q k^T +
+// position_bias, no 1 / sqrt(d) -- the caller passes scale = 1) selects the RB kernels, drop_p > 0
+// the DROP ones; lse and drop_bits are written when given.  At drop_p = 0 the training forward
+// runs the inference kernels: the same ctx bits.
+static int attention_fwd(const void* qkv, const int64_t* mask, bool rb, const float* relbias, void* ctx, float* lse,
+                         uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
+                         float drop_p, uint64_t seed, uint64_t site, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  if (B == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx && (!rb || relbias));
+  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, lse, drop_p, seed, site,
+             drop_bits, relbias};
+  using Kernel = void (*)(AttnArgs);
+#define DRT_AF_ROW(NB)                                                          \
+  {{attention_fwd_kernel<NB, false, false>, attention_fwd_kernel<NB, false, true>}, \
+   {attention_fwd_kernel<NB, true, false>, attention_fwd_kernel<NB, true, true>}}
+  // [NB][drop][rb]; NB = 0: 161 <= L <= 512 (the backward's streamed kernels)
+  static constexpr Kernel kernels[6][2][2] = {DRT_AF_ROW(0), DRT_AF_ROW(1), DRT_AF_ROW(2),
+                                              DRT_AF_ROW(3), DRT_AF_ROW(4), DRT_AF_ROW(5)};
+#undef DRT_AF_ROW
+  const bool drop = drop_p > 0.0f;
+  const int Lp = ((int)L + 31) & ~31;
+  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (rb ? (size_t)Lp * 8 : 0);
+  static bool attr_set = false;
+  if (!attr_set) {   // L > 224 stages more than the default 64 KiB
+    for (const auto& by_drop : kernels)
+      for (const auto& by_rb : by_drop)
+        for (const Kernel k : by_rb)
+          DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  void* args[] = {&a};
+  hipLaunchKernel((const void*)kernels[nb][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
+                  (hipStream_t)stream);
+  return hip_status(hipGetLastError());
+}
+
 }  // namespace drt
 
 using namespace drt;
 
 extern "C" {
-
-int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
-                     const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
-                     int32_t H, void* out, void* pre, void* stream);
 
 int drt_gelu_bf16(const void* x, int64_t n, void* y, void* stream) {
   DRT_REQUIRE(n >= 0);
@@ -599,9 +635,8 @@ int drt_gelu_bf16(const void* x, int64_t n, void* y, void* stream) {
   return hip_status(hipGetLastError());
 }
 
-int drt_embedding_bwd_types(const int64_t* ids, const int64_t* type_ids, int32_t ntypes, const void* d, int64_t B,
-                            int64_t L, int32_t H, int64_t padding_idx, float* dword, float* dpos, float* dtype,
-                            void* stream) {
+int drt_embedding_bwd(const int64_t* ids, const int64_t* type_ids, int32_t ntypes, const void* d, int64_t B, int64_t L,
+                      int32_t H, int64_t padding_idx, float* dword, float* dpos, float* dtype, void* stream) {
   DRT_REQUIRE(B >= 0 && L > 0 && H > 0 && ntypes >= 1 && (type_ids == nullptr || ntypes <= kMaxTypes));
   if (B == 0) return DRT_OK;
   DRT_REQUIRE(ids && d && dword && dpos && dtype);
@@ -621,17 +656,6 @@ int drt_embedding_bwd_types(const int64_t* ids, const int64_t* type_ids, int32_t
   return hip_status(hipGetLastError());
 }
 
-int drt_embedding_bwd(const int64_t* ids, const int64_t* type_ids, const void* d, int64_t B, int64_t L, int32_t H,
-                      int64_t padding_idx, float* dword, float* dpos, float* dtype, void* stream) {
-  return drt_embedding_bwd_types(ids, type_ids, type_ids ? 2 : 1, d, B, L, H, padding_idx, dword, dpos, dtype, stream);
-}
-
-int drt_embed_ln(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
-                 const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
-                 int32_t H, void* out, void* stream) {
-  return drt_embed_ln_pre(ids, type_ids, B, L, word_emb, pos_emb, type_emb, gamma, beta, eps, H, out, nullptr, stream);
-}
-
 int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
                      const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
                      int32_t H, void* out, void* pre, void* stream) {
@@ -641,19 +665,18 @@ int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int
   DRT_REQUIRE(ids && word_emb && pos_emb && type_emb && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((T + 3) / 4));
-  __bf16* o = (__bf16*)out;
-  __bf16* p = (__bf16*)pre;
-#define EMB(E) hipLaunchKernelGGL(embed_ln_kernel<E>, grid, dim3(256), 0, s, ids, type_ids, T, L, word_emb, pos_emb, \
-                                  type_emb, gamma, beta, eps, (int)H, o, p)
-  switch (H / 64) {
-    case 4: EMB(4); break;
-    case 8: EMB(8); break;
-    case 12: EMB(12); break;
-    case 16: EMB(16); break;
-    default: return DRT_EINVAL;
-  }
-#undef EMB
+  if (const int rc = dispatch_epl(H, [&](auto E) {
+        hipLaunchKernelGGL(embed_ln_kernel<decltype(E)::value>, grid, dim3(256), 0, s, ids, type_ids, T, L, word_emb,
+                           pos_emb, type_emb, gamma, beta, eps, (int)H, (__bf16*)out, (__bf16*)pre);
+      }))
+    return rc;
   return hip_status(hipGetLastError());
+}
+
+int drt_embed_ln(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
+                 const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
+                 int32_t H, void* out, void* stream) {
+  return drt_embed_ln_pre(ids, type_ids, B, L, word_emb, pos_emb, type_emb, gamma, beta, eps, H, out, nullptr, stream);
 }
 
 int drt_layernorm_f32_bf16(const float* X, int64_t M, int32_t H, const float* gamma, const float* beta, float eps,
@@ -663,13 +686,11 @@ int drt_layernorm_f32_bf16(const float* X, int64_t M, int32_t H, const float* ga
   DRT_REQUIRE(X && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((M + 3) / 4));
-  switch (H / 64) {
-    case 4: hipLaunchKernelGGL(layernorm_f32_kernel<4>, grid, dim3(256), 0, s, X, M, H, gamma, beta, eps, (__bf16*)out); break;
-    case 8: hipLaunchKernelGGL(layernorm_f32_kernel<8>, grid, dim3(256), 0, s, X, M, H, gamma, beta, eps, (__bf16*)out); break;
-    case 12: hipLaunchKernelGGL(layernorm_f32_kernel<12>, grid, dim3(256), 0, s, X, M, H, gamma, beta, eps, (__bf16*)out); break;
-    case 16: hipLaunchKernelGGL(layernorm_f32_kernel<16>, grid, dim3(256), 0, s, X, M, H, gamma, beta, eps, (__bf16*)out); break;
-    default: return DRT_EINVAL;
-  }
+  if (const int rc = dispatch_epl(H, [&](auto E) {
+        hipLaunchKernelGGL(layernorm_f32_kernel<decltype(E)::value>, grid, dim3(256), 0, s, X, M, H, gamma, beta, eps,
+                           (__bf16*)out);
+      }))
+    return rc;
   return hip_status(hipGetLastError());
 }
 
@@ -679,151 +700,48 @@ int drt_layernorm_bf16(const void* X, int64_t M, int32_t H, const float* gamma, 
   if (M == 0) return DRT_OK;
   DRT_REQUIRE(X && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
-  const __bf16* x = (const __bf16*)X;
-  __bf16* o = (__bf16*)out;
   dim3 grid(ln_rows_grid(M));
-  switch (H / 64) {
-    case 4: hipLaunchKernelGGL(layernorm_bf16_kernel<4>, grid, dim3(256), 0, s, x, M, H, gamma, beta, eps, o); break;
-    case 8: hipLaunchKernelGGL(layernorm_bf16_kernel<8>, grid, dim3(256), 0, s, x, M, H, gamma, beta, eps, o); break;
-    case 12: hipLaunchKernelGGL(layernorm_bf16_kernel<12>, grid, dim3(256), 0, s, x, M, H, gamma, beta, eps, o); break;
-    case 16: hipLaunchKernelGGL(layernorm_bf16_kernel<16>, grid, dim3(256), 0, s, x, M, H, gamma, beta, eps, o); break;
-    default: return DRT_EINVAL;
-  }
+  if (const int rc = dispatch_epl(H, [&](auto E) {
+        hipLaunchKernelGGL(layernorm_bf16_kernel<decltype(E)::value>, grid, dim3(256), 0, s, (const __bf16*)X, M, H,
+                           gamma, beta, eps, (__bf16*)out);
+      }))
+    return rc;
   return hip_status(hipGetLastError());
 }
 
-int drt_attention_fwd_lse_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B, int64_t L,
-                               int32_t heads, int32_t head_dim, float scale, void* stream);
-
 int drt_attention_bf16(const void* qkv, const int64_t* mask, void* ctx, int64_t B, int64_t L, int32_t heads,
                        int32_t head_dim, float scale, void* stream) {
-  return drt_attention_fwd_lse_bf16(qkv, mask, ctx, nullptr, B, L, heads, head_dim, scale, stream);
+  return attention_fwd(qkv, mask, false, nullptr, ctx, nullptr, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
 }
-
-int drt_attention_train_fwd_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B, int64_t L,
-                                 int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                 uint64_t site, void* stream);
 
 int drt_attention_fwd_lse_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B, int64_t L,
                                int32_t heads, int32_t head_dim, float scale, void* stream) {
-  return drt_attention_train_fwd_bf16(qkv, mask, ctx, lse, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
+  return attention_fwd(qkv, mask, false, nullptr, ctx, lse, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
 }
 
-int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse,
-                                      uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
-                                      float scale, float drop_p, uint64_t seed, uint64_t site, void* stream);
-
-int drt_attention_train_fwd_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B, int64_t L,
-                                 int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                 uint64_t site, void* stream) {
-  return drt_attention_train_fwd_bits_bf16(qkv, mask, ctx, lse, nullptr, B, L, heads, head_dim, scale, drop_p, seed,
-                                           site, stream);
-}
-
-// The training forward that also writes the attention-dropout keep mask as bits (drop_bits, when
-// drop_p > 0 and drop_bits != NULL): [B][heads][L][ceil(L / 32)] u32, bit (key & 31) of word
+// The training forward: lse, attention-probability dropout and (when drop_p > 0 and drop_bits !=
+// NULL) the keep mask as bits, [B][heads][L][ceil(L / 32)] u32, bit (key & 31) of word
 // (query, key >> 5); drt_attention_train_bwd_bits_bf16 reads it instead of regenerating the hash.
 int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse,
                                       uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
                                       float scale, float drop_p, uint64_t seed, uint64_t site, void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  if (B == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx);
-  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, lse, drop_p, seed, site,
-             drop_bits};
-  const int Lp = ((int)L + 31) & ~31;
-  const int nb = Lp / 32;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* ks[] = {(const void*)attention_fwd_kernel<0, false>, (const void*)attention_fwd_kernel<4, false>,
-                        (const void*)attention_fwd_kernel<5, false>, (const void*)attention_fwd_kernel<4, true>,
-                        (const void*)attention_fwd_kernel<5, true>, (const void*)attention_fwd_kernel<0, true>};
-    for (const void* f : ks) DRT_CHECK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  const dim3 grid((unsigned)(B * heads));
-  hipStream_t s = (hipStream_t)stream;
-  const bool drop = drop_p > 0.0f;
-#define DRT_AF_LAUNCH(NB_)                                                                              \
-  case NB_: {                                                                                           \
-    const dim3 blk(NB_ == 5 ? 320 : 256);                                                               \
-    if (drop) hipLaunchKernelGGL((attention_fwd_kernel<NB_, true>), grid, blk, lds, s, a);             \
-    else hipLaunchKernelGGL((attention_fwd_kernel<NB_, false>), grid, blk, lds, s, a);                 \
-    break;                                                                                              \
-  }
-  switch (nb) {
-    DRT_AF_LAUNCH(1)
-    DRT_AF_LAUNCH(2)
-    DRT_AF_LAUNCH(3)
-    DRT_AF_LAUNCH(4)
-    DRT_AF_LAUNCH(5)
-    default:   // 161 <= L <= 512 (the backward's streamed kernels)
-      if (drop) hipLaunchKernelGGL((attention_fwd_kernel<0, true>), grid, dim3(256), lds, s, a);
-      else hipLaunchKernelGGL((attention_fwd_kernel<0, false>), grid, dim3(256), lds, s, a);
-      break;
-  }
-#undef DRT_AF_LAUNCH
-  return hip_status(hipGetLastError());
+  return attention_fwd(qkv, mask, false, nullptr, ctx, lse, drop_bits, B, L, heads, head_dim, scale, drop_p, seed, site,
+                       stream);
 }
 
-// The inference forward with a relative-position bias (T5Attention, modeling_t5.py: scores =
-// q k^T + position_bias, no 1 / sqrt(d) -- the caller passes scale = 1): relbias fp32
-// [heads][2 L - 1], entry (head, key - query + L - 1).  The RB instantiations of the kernel above;
-// attention_relbias_launch serves it (drop = false) and the training forward below.
-static int attention_relbias_launch(const AttnArgs& a, bool drop, hipStream_t s) {
-  const int Lp = ((int)a.L + 31) & ~31;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (size_t)Lp * 8;
-  static bool attr_set = false;
-  if (!attr_set) {   // L > 224 stages more than the default 64 KiB (only the NB = 0 kernels get there)
-    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)attention_fwd_kernel<0, false, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    DRT_CHECK_HIP(hipFuncSetAttribute((const void*)attention_fwd_kernel<0, true, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  const dim3 grid((unsigned)(a.B * a.heads));
-#define DRT_ARB_LAUNCH(NB_, NT_)                                                                          \
-  if (drop) hipLaunchKernelGGL((attention_fwd_kernel<NB_, true, true>), grid, dim3(NT_), lds, s, a);      \
-  else hipLaunchKernelGGL((attention_fwd_kernel<NB_, false, true>), grid, dim3(NT_), lds, s, a);          \
-  break;
-  switch (Lp / 32) {
-    case 1: DRT_ARB_LAUNCH(1, 256)
-    case 2: DRT_ARB_LAUNCH(2, 256)
-    case 3: DRT_ARB_LAUNCH(3, 256)
-    case 4: DRT_ARB_LAUNCH(4, 256)
-    case 5: DRT_ARB_LAUNCH(5, 320)
-    default: DRT_ARB_LAUNCH(0, 256)
-  }
-#undef DRT_ARB_LAUNCH
-  return hip_status(hipGetLastError());
-}
-
+// The same two with a relative-position bias: relbias fp32 [heads][2 L - 1], entry
+// (head, key - query + L - 1).
 int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx, int64_t B,
                                int64_t L, int32_t heads, int32_t head_dim, float scale, void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
-  if (B == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx && relbias);
-  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, nullptr, 0.0f, 0, 0,
-             nullptr, relbias};
-  return attention_relbias_launch(a, false, (hipStream_t)stream);
+  return attention_fwd(qkv, mask, true, relbias, ctx, nullptr, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
 }
 
-// The training forward of T5Attention: drt_attention_train_fwd_bits_bf16 (lse, attention-probability
-// dropout, keep bits) with the relative-position bias of drt_attention_relbias_bf16.  At drop_p = 0
-// the same kernels as drt_attention_relbias_bf16: the same ctx bits.
 int drt_attention_relbias_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx,
                                               float* lse, uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads,
                                               int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                               uint64_t site, void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  if (B == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx && relbias);
-  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, lse, drop_p, seed, site,
-             drop_bits, relbias};
-  return attention_relbias_launch(a, drop_p > 0.0f, (hipStream_t)stream);
+  return attention_fwd(qkv, mask, true, relbias, ctx, lse, drop_bits, B, L, heads, head_dim, scale, drop_p, seed, site,
+                       stream);
 }
 
 int drt_pool_bf16(const void* hidden, const int64_t* mask, int64_t B, int64_t L, int32_t H, int32_t mode,

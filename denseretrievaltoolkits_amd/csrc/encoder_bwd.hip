@@ -12,6 +12,7 @@
 //   transpose_bf16  y[c][r] = x[r][c]                 (operand layout for weight gradients)
 //   attention_bwd   dQ, dK, dV of softmax(Q K^T / sqrt(dh) + mask) V  (L <= 160)
 #include "drt_common.h"
+#include "ln_row.h"
 
 namespace drt {
 
@@ -1231,6 +1232,87 @@ static int colsum_launch(const T* x, int64_t M, int64_t N, float* out, float* ws
   return hip_status(hipGetLastError());
 }
 
+// Rows of the work-groups' partial sums (dbias, dtable): one per sequence (L <= 160) or per
+// (sequence, 128-query group).
+static int64_t attention_bwd_rows(int64_t B, int64_t L) {
+  return L > kAbMaxSeq ? B * ((L + kAblGroup - 1) / kAblGroup) : B;
+}
+
+// The host driver behind the attention backward entries below (drt_attention_bwd_bf16, _train_bwd_bits,
+// _train_bwd_bias, _relbias_train_bwd): dqkv [B*L][3H] (dQ | dK | dV, head-major like qkv) of the
+// attention forward, given dctx = dO, the forward's ctx = O, lse and (drop_p, seed, site).
+// drop_bits: the forward's keep bits, read instead of re-hashing every (query, key) twice (dK / dV
+// and dQ phases); NULL = regenerate from the hash (L <= 160 only).  relbias: the forward's
+// relative-position bias, joins the score rebuild and comes with its gradient dtable [heads][2L-1]
+// -- the work-groups' diagonal sums of the fp32 dS (in ws), summed over the sequences in a fixed
+// order.  dbias [3H] = the column sums of dQKV (the query / key / value bias gradients) from partials
+// the kernels leave in ws, reduced in a fixed order -- no pass over dQKV.  No entry passes both
+// dbias and dtable: they share ws.
+static int attention_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int64_t* mask,
+                         const float* relbias, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
+                         int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
+                         float* dbias, float* dtable, void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && L <= kAblMaxSeq && heads > 0 && head_dim == 64);
+  DRT_REQUIRE(!relbias == !dtable);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  float* part = dbias || dtable ? (float*)ws : nullptr;   // the kernels' partial sums
+  if (dbias || dtable)
+    DRT_REQUIRE(B > 0 && ws && ws_bytes >= (dbias ? drt_attention_train_bwd_bias_workspace(B, heads, head_dim)
+                                                   : drt_attention_relbias_train_bwd_workspace(B, L, heads)));
+  if (B == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx && dctx && lse && dqkv);
+  AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, mask, (__bf16*)dqkv, B, L,
+                heads, heads * 64, scale, drop_p, seed, site, drop_bits, dbias ? part : nullptr, relbias,
+                dtable ? part : nullptr};
+  using Kernel = void (*)(AttnBwdArgs);
+  // [drop][rb], the whole-sequence kernels [NB - 1][drop][rb]
+#define DRT_AB_LONG(K) {{K<false, false>, K<false, true>}, {K<true, false>, K<true, true>}}
+#define DRT_AB_RK(NB)                                                                     \
+  {{attention_bwd_rk_kernel<NB, false, false>, attention_bwd_rk_kernel<NB, false, true>}, \
+   {attention_bwd_rk_kernel<NB, true, false>, attention_bwd_rk_kernel<NB, true, true>}}
+  static constexpr Kernel long_dkdv[2][2] = DRT_AB_LONG(attention_bwd_long_dkdv_kernel);
+  static constexpr Kernel long_dq[2][2] = DRT_AB_LONG(attention_bwd_long_dq_kernel);
+  static constexpr Kernel rk[5][2][2] = {DRT_AB_RK(1), DRT_AB_RK(2), DRT_AB_RK(3), DRT_AB_RK(4), DRT_AB_RK(5)};
+#undef DRT_AB_RK
+#undef DRT_AB_LONG
+  const bool drop = drop_p > 0.0f, rb = relbias != nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  void* args[] = {&a};
+  if (L > kAbMaxSeq) {   // streamed kernels: dK / dV over key groups, dQ over query groups
+    DRT_REQUIRE(!drop || drop_bits);   // the forward's keep bits
+    const dim3 grid((unsigned)(B * heads), (unsigned)((L + kAblGroup - 1) / kAblGroup));
+    hipLaunchKernel((const void*)long_dkdv[drop][rb], grid, dim3(256), args, 0, st);
+    hipLaunchKernel((const void*)long_dq[drop][rb], grid, dim3(256), args, 0, st);
+  } else {
+    const int Lp = ((int)L + 31) & ~31;
+    const int nb = Lp / 32;
+    // register-resident P / dS; dropout from the forward's keep bits (or the same bits drawn again)
+    const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + (drop ? (size_t)nb * Lp * 4 : 0) +
+                       (rb ? (size_t)4 * Lp * 4 + (size_t)4 * (2 * Lp + 4) * 4 : 0);   // RB: the bias diagonals and
+                                                // their gradient, 2 Lp floats each, + 4 shifted reversed copies
+    DRT_REQUIRE(lds <= 160 * 1024);
+    static bool rk_attr = false;
+    if (!rk_attr) {
+      for (const auto& by_drop : rk)
+        for (const auto& by_rb : by_drop)
+          for (const Kernel k : by_rb)
+            DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      rk_attr = true;
+    }
+    hipLaunchKernel((const void*)rk[nb - 1][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 512 : 256), args,
+                    lds, st);
+  }
+  const int rc = hip_status(hipGetLastError());
+  if (rc || !part) return rc;
+  const int64_t rows = attention_bwd_rows(B, L);
+  if (dbias) {
+    const int64_t n = 3 * (int64_t)heads * head_dim;
+    return colsum_launch<float>(part, rows, n, dbias, part + (size_t)B * (kAblMaxSeq / kAblGroup) * n, st);
+  }
+  const int64_t n = (int64_t)heads * (2 * L - 1);
+  return colsum_launch<float>(part, rows, n, dtable, part + (size_t)rows * n, st);
+}
+
 }  // namespace drt
 
 using namespace drt;
@@ -1270,32 +1352,10 @@ size_t drt_layernorm_bwd_workspace(int64_t M, int32_t H) {
 
 // dx = LN backward of dy through out = LN(x) (gamma; x = the bf16 pre-LN sums the forward
 // stored) + dres (residual gradient, may be NULL); dgamma / dbeta fp32 [H] (deterministic).
-int drt_layernorm_bwd_drop_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
-                                const void* dres, void* dx, void* dx_drop, float drop_p, uint64_t seed, uint64_t site,
-                                float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
-
-int drt_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
-                           const void* dres, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
-                           void* stream) {
-  return drt_layernorm_bwd_drop_bf16(dy, x, gamma, eps, M, H, dres, dx, nullptr, 0.f, 0, 0, dgamma, dbeta, ws,
-                                     ws_bytes, stream);
-}
-
-int drt_layernorm_bwd_sum_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
-                               const void* dres, void* dx, void* dx_drop, float drop_p, uint64_t seed, uint64_t site,
-                               float* dgamma, float* dbeta, float* dsum, void* ws, size_t ws_bytes, void* stream);
-
-// The same, also writing dx_drop = dropout(dx) with drt_dropout_add_bf16's mask of (drop_p, seed, site)
-// (the gradient entering the linear whose output HF dropped before this LayerNorm's residual add).
-int drt_layernorm_bwd_drop_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
-                                const void* dres, void* dx, void* dx_drop, float drop_p, uint64_t seed, uint64_t site,
-                                float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
-  return drt_layernorm_bwd_sum_bf16(dy, x, gamma, eps, M, H, dres, dx, dx_drop, drop_p, seed, site, dgamma, dbeta,
-                                    nullptr, ws, ws_bytes, stream);
-}
-
-// The same, also writing dsum [H] fp32 = the column sums of the gradient it hands down (dx_drop,
-// or dx without dropout) -- the bias gradient of the linear feeding this LayerNorm.
+// dx_drop (optional) = dropout(dx) with drt_dropout_add_bf16's mask of (drop_p, seed, site): the
+// gradient entering the linear whose output HF dropped before this LayerNorm's residual add.
+// dsum (optional) [H] fp32 = the column sums of the gradient handed down (dx_drop, or dx without
+// dropout) -- the bias gradient of the linear feeding this LayerNorm.
 int drt_layernorm_bwd_sum_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
                                const void* dres, void* dx, void* dx_drop, float drop_p, uint64_t seed, uint64_t site,
                                float* dgamma, float* dbeta, float* dsum, void* ws, size_t ws_bytes, void* stream) {
@@ -1304,28 +1364,29 @@ int drt_layernorm_bwd_sum_bf16(const void* dy, const void* x, const float* gamma
   DRT_REQUIRE(dy && x && gamma && dx && dgamma && dbeta && ws && ws_bytes >= drt_layernorm_bwd_workspace(M, H));
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)ws;   // [3 * blocks][H]: dgamma rows, dbeta rows, dsum rows
-  const dim3 grid(kLnBwdBlocks);
-#define LNB(E, S)                                                                                                   \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<E, S>), grid, dim3(256), 0, s, (const __bf16*)dy, (const __bf16*)x, gamma, \
-                     eps, M, (int)H, (const __bf16*)dres, (__bf16*)dx, part, (__bf16*)dx_drop, drop_p, seed, site)
-#define LNB2(E) \
-  if (dsum) LNB(E, true); \
-  else LNB(E, false);
-  switch (H / 64) {
-    case 4: LNB2(4); break;
-    case 8: LNB2(8); break;
-    case 12: LNB2(12); break;
-    case 16: LNB2(16); break;
-    default: return DRT_EINVAL;
-  }
-#undef LNB2
-#undef LNB
+  auto launch = [&](auto E, auto SUM) {
+    hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(E)::value, decltype(SUM)::value>), dim3(kLnBwdBlocks), dim3(256),
+                       0, s, (const __bf16*)dy, (const __bf16*)x, gamma, eps, M, (int)H, (const __bf16*)dres,
+                       (__bf16*)dx, part, (__bf16*)dx_drop, drop_p, seed, site);
+  };
+  int rc = dispatch_epl(H, [&](auto E) {
+    if (dsum) launch(E, std::true_type{});
+    else launch(E, std::false_type{});
+  });
+  if (rc) return rc;
   float* ws2 = part + (size_t)3 * kLnBwdBlocks * H;
-  int rc = colsum_launch<float>(part, kLnBwdBlocks, H, dgamma, ws2, s);
+  rc = colsum_launch<float>(part, kLnBwdBlocks, H, dgamma, ws2, s);
   if (rc) return rc;
   rc = colsum_launch<float>(part + (size_t)kLnBwdBlocks * H, kLnBwdBlocks, H, dbeta, ws2, s);
   if (rc || !dsum) return rc;
   return colsum_launch<float>(part + (size_t)2 * kLnBwdBlocks * H, kLnBwdBlocks, H, dsum, ws2, s);
+}
+
+int drt_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
+                           const void* dres, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                           void* stream) {
+  return drt_layernorm_bwd_sum_bf16(dy, x, gamma, eps, M, H, dres, dx, nullptr, 0.f, 0, 0, dgamma, dbeta, nullptr, ws,
+                                    ws_bytes, stream);
 }
 
 int drt_gelu_bwd_bf16(const void* dy, const void* pre, int64_t n, void* dx, void* stream) {
@@ -1338,178 +1399,52 @@ int drt_gelu_bwd_bf16(const void* dy, const void* pre, int64_t n, void* dx, void
   return hip_status(hipGetLastError());
 }
 
-// dqkv [B*L][3H] (dQ | dK | dV, head-major like qkv) of the attention forward
-// (drt_attention_fwd_lse_bf16) given dctx = dO, the forward's ctx = O and lse.  L <= 160.
-int drt_attention_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                 const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads,
-                                 int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
-                                 void* stream);
+// Sized for any L <= 512: per-(sequence, 128-row group) partials [B][G <= 4][3H] + the colsum's own.
+size_t drt_attention_train_bwd_bias_workspace(int64_t B, int32_t heads, int32_t head_dim) {
+  if (B <= 0 || heads <= 0 || head_dim <= 0) return 0;
+  const int64_t n = 3 * (int64_t)heads * head_dim, rows = B * (kAblMaxSeq / kAblGroup);
+  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
+}
+
+// One row [heads][2L-1] per work-group (attention_bwd_rows), then the column sum's own scratch.
+size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads) {
+  if (B <= 0 || L <= 0 || L > kAblMaxSeq || heads <= 0) return 0;
+  const int64_t n = (int64_t)heads * (2 * L - 1), rows = attention_bwd_rows(B, L);
+  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
+}
 
 int drt_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                            const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
                            float scale, void* stream) {
-  return drt_attention_train_bwd_bf16(qkv, ctx, dctx, lse, mask, dqkv, B, L, heads, head_dim, scale, 0.0f, 0, 0,
-                                      stream);
+  return attention_bwd(qkv, ctx, dctx, lse, mask, nullptr, nullptr, dqkv, B, L, heads, head_dim, scale, 0.0f, 0, 0,
+                       nullptr, nullptr, nullptr, 0, stream);
 }
-
-// The same with the forward's attention-probability dropout (drop_p, seed, site as passed to
-// drt_attention_train_fwd_bf16).
-int drt_attention_train_bwd_bits_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                      const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
-                                      int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                      uint64_t site, void* stream);
-
-int drt_attention_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                 const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads,
-                                 int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
-                                 void* stream) {
-  return drt_attention_train_bwd_bits_bf16(qkv, ctx, dctx, lse, mask, nullptr, dqkv, B, L, heads, head_dim, scale,
-                                           drop_p, seed, site, stream);
-}
-
-// The same reading the forward's keep bits (drt_attention_train_fwd_bits_bf16) instead of re-hashing
-// every (query, key) twice (dK / dV and dQ phases); NULL drop_bits = regenerate from the hash.
-static int attention_bwd_launch(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
-                                int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                uint64_t site, float* dsum_part, void* stream, const float* relbias = nullptr,
-                                float* dtab_part = nullptr);
 
 int drt_attention_train_bwd_bits_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                       const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
                                       int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                       uint64_t site, void* stream) {
-  return attention_bwd_launch(qkv, ctx, dctx, lse, mask, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
-                              site, nullptr, stream);
+  return attention_bwd(qkv, ctx, dctx, lse, mask, nullptr, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
+                       site, nullptr, nullptr, nullptr, 0, stream);
 }
 
-// Sized for any L <= 512: per-(sequence, 128-row group) partials [B][G <= 4][3H] + the colsum's own.
-size_t drt_attention_train_bwd_bias_workspace(int64_t B, int32_t heads, int32_t head_dim) {
-  if (B <= 0 || heads <= 0 || head_dim <= 0) return 0;
-  const int64_t n = 3 * (int64_t)heads * head_dim;
-  const int64_t gmax = kAblMaxSeq / kAblGroup;
-  return (size_t)B * gmax * n * sizeof(float) + drt_colsum_workspace(B * gmax, n);
-}
-
-// The same, also writing dbias [3H] fp32 = the column sums of dQKV (the query / key / value
-// bias gradients) from per-sequence (L > 160: per 128-row group) partials the kernels leave in ws,
-// reduced in a fixed order -- no pass over dQKV.
 int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                       const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
                                       int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                       uint64_t site, float* dbias, void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(dbias && B > 0 && ws && ws_bytes >= drt_attention_train_bwd_bias_workspace(B, heads, head_dim));
-  float* part = (float*)ws;
-  int rc = attention_bwd_launch(qkv, ctx, dctx, lse, mask, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p,
-                                seed, site, part, stream);
-  if (rc) return rc;
-  const int64_t n = 3 * (int64_t)heads * head_dim;
-  const int64_t rows = L > kAbMaxSeq ? B * ((L + kAblGroup - 1) / kAblGroup) : B;
-  const int64_t gmax = kAblMaxSeq / kAblGroup;
-  return colsum_launch<float>(part, rows, n, dbias, part + (size_t)B * gmax * n, (hipStream_t)stream);
+  DRT_REQUIRE(dbias);
+  return attention_bwd(qkv, ctx, dctx, lse, mask, nullptr, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
+                       site, dbias, nullptr, ws, ws_bytes, stream);
 }
 
-// Work-group rows of the relative-bias gradient: one per sequence (L <= 160) or per (sequence,
-// 128-query group), each [heads][2L-1] fp32; then the column sum's own scratch.
-static int64_t relbias_bwd_rows(int64_t B, int64_t L) {
-  return L > kAbMaxSeq ? B * ((L + kAblGroup - 1) / kAblGroup) : B;
-}
-size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads) {
-  if (B <= 0 || L <= 0 || L > kAblMaxSeq || heads <= 0) return 0;
-  const int64_t n = (int64_t)heads * (2 * L - 1), rows = relbias_bwd_rows(B, L);
-  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
-}
-
-// T5Attention backward: drt_attention_train_bwd_bits_bf16 with the forward's relative-position bias
-// relbias fp32 [heads][2L-1] in the score rebuild, also writing its gradient dtable [heads][2L-1]:
-// the work-groups' diagonal sums of the fp32 dS (in ws), summed over the sequences in a fixed order.
 int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                          const int64_t* mask, const float* relbias, const uint32_t* drop_bits,
                                          void* dqkv, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
                                          float scale, float drop_p, uint64_t seed, uint64_t site, float* dtable,
                                          void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(B > 0 && L > 0 && L <= kAblMaxSeq && heads > 0 && relbias && dtable && ws);
-  DRT_REQUIRE(ws_bytes >= drt_attention_relbias_train_bwd_workspace(B, L, heads));
-  float* part = (float*)ws;
-  const int rc = attention_bwd_launch(qkv, ctx, dctx, lse, mask, drop_bits, dqkv, B, L, heads, head_dim, scale,
-                                      drop_p, seed, site, nullptr, stream, relbias, part);
-  if (rc) return rc;
-  const int64_t n = (int64_t)heads * (2 * L - 1), rows = relbias_bwd_rows(B, L);
-  return colsum_launch<float>(part, rows, n, dtable, part + (size_t)rows * n, (hipStream_t)stream);
-}
-
-static int attention_bwd_launch(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
-                                int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                uint64_t site, float* dsum_part, void* stream, const float* relbias,
-                                float* dtab_part) {
-  DRT_REQUIRE(B >= 0 && L > 0 && L <= kAblMaxSeq && heads > 0 && head_dim == 64);
-  DRT_REQUIRE(!relbias == !dtab_part);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  if (B == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx && dctx && lse && dqkv);
-  AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, mask, (__bf16*)dqkv, B, L,
-                heads, heads * 64, scale, drop_p, seed, site, drop_bits, dsum_part, relbias, dtab_part};
-  const bool rb = relbias != nullptr;
-  if (L > kAbMaxSeq) {   // streamed kernels: dK / dV over key groups, dQ over query groups
-    const bool drop = drop_p > 0.0f;
-    DRT_REQUIRE(!drop || drop_bits);   // the forward's keep bits (drt_attention_train_fwd_bits_bf16)
-    const dim3 grid((unsigned)(B * heads), (unsigned)((L + kAblGroup - 1) / kAblGroup));
-    hipStream_t st = (hipStream_t)stream;
-    if (rb && drop) {
-      hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<true, true>), grid, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attention_bwd_long_dq_kernel<true, true>), grid, dim3(256), 0, st, a);
-    } else if (rb) {
-      hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<false, true>), grid, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attention_bwd_long_dq_kernel<false, true>), grid, dim3(256), 0, st, a);
-    } else if (drop) {
-      hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<true>), grid, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attention_bwd_long_dq_kernel<true>), grid, dim3(256), 0, st, a);
-    } else {
-      hipLaunchKernelGGL((attention_bwd_long_dkdv_kernel<false>), grid, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attention_bwd_long_dq_kernel<false>), grid, dim3(256), 0, st, a);
-    }
-    return hip_status(hipGetLastError());
-  }
-  const int Lp = ((int)L + 31) & ~31;
-  const int nb = Lp / 32;
-  const dim3 grid((unsigned)(B * heads));
-  const bool drop = drop_p > 0.0f;
-  // register-resident P / dS; dropout from the forward's keep bits (or the same bits drawn again)
-  size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + (drop ? (size_t)nb * Lp * 4 : 0) +
-               (rb ? (size_t)4 * Lp * 4 + (size_t)4 * (2 * Lp + 4) * 4 : 0);   // RB: the bias diagonals and their
-                                                // gradient, 2 Lp floats each, + 4 shifted reversed copies
-  DRT_REQUIRE(lds <= 160 * 1024);
-  static bool rk_attr = false;
-  if (!rk_attr) {
-    const void* ks[] = {(const void*)attention_bwd_rk_kernel<4, false>, (const void*)attention_bwd_rk_kernel<4, true>,
-                        (const void*)attention_bwd_rk_kernel<5, false>, (const void*)attention_bwd_rk_kernel<5, true>,
-                        (const void*)attention_bwd_rk_kernel<4, false, true>,
-                        (const void*)attention_bwd_rk_kernel<4, true, true>,
-                        (const void*)attention_bwd_rk_kernel<5, false, true>,
-                        (const void*)attention_bwd_rk_kernel<5, true, true>};
-    for (const void* f : ks) DRT_CHECK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    rk_attr = true;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 blk(nb == 5 ? 512 : 256);
-#define DRT_AB_LAUNCH(NB_)                                                                              \
-  case NB_:                                                                                             \
-    if (rb && drop) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, true, true>), grid, blk, lds, st, a);  \
-    else if (rb) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, false, true>), grid, blk, lds, st, a);    \
-    else if (drop) hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, true>), grid, blk, lds, st, a);    \
-    else hipLaunchKernelGGL((attention_bwd_rk_kernel<NB_, false>), grid, blk, lds, st, a);             \
-    break;
-  switch (nb) {
-    DRT_AB_LAUNCH(1)
-    DRT_AB_LAUNCH(2)
-    DRT_AB_LAUNCH(3)
-    DRT_AB_LAUNCH(4)
-    DRT_AB_LAUNCH(5)
-    default: return DRT_EINVAL;
-  }
-#undef DRT_AB_LAUNCH
-  return hip_status(hipGetLastError());
+  DRT_REQUIRE(relbias && dtable);
+  return attention_bwd(qkv, ctx, dctx, lse, mask, relbias, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
+                       site, nullptr, dtable, ws, ws_bytes, stream);
 }
 
 int drt_dropout_add_bf16(const void* y, const void* resid, int64_t n, float p, uint64_t seed, uint64_t site,

@@ -1286,17 +1286,11 @@ extern "C" int drt_linear_ln_bf16_ws(const void* X, const void* W, const float* 
   launch_small<true, EPI_BIAS | EPI_RESID, true>(b, tiles, p.splits, s);
   const dim3 grid((unsigned)((M + 3) / 4));
   const int splits = p.splits;
-  switch (N / 64) {
-    case 4: hipLaunchKernelGGL(splitk_ln_kernel<4>, grid, dim3(256), 0, s, (const float*)ws, splits, M, (int)N, 1.0f,
-                               bias, (const __bf16*)residual, gamma, beta, eps, (__bf16*)out); break;
-    case 8: hipLaunchKernelGGL(splitk_ln_kernel<8>, grid, dim3(256), 0, s, (const float*)ws, splits, M, (int)N, 1.0f,
-                               bias, (const __bf16*)residual, gamma, beta, eps, (__bf16*)out); break;
-    case 12: hipLaunchKernelGGL(splitk_ln_kernel<12>, grid, dim3(256), 0, s, (const float*)ws, splits, M, (int)N, 1.0f,
-                                bias, (const __bf16*)residual, gamma, beta, eps, (__bf16*)out); break;
-    case 16: hipLaunchKernelGGL(splitk_ln_kernel<16>, grid, dim3(256), 0, s, (const float*)ws, splits, M, (int)N, 1.0f,
-                                bias, (const __bf16*)residual, gamma, beta, eps, (__bf16*)out); break;
-    default: return DRT_EINVAL;
-  }
+  if (const int rc = dispatch_epl(N, [&](auto E) {
+        hipLaunchKernelGGL(splitk_ln_kernel<decltype(E)::value>, grid, dim3(256), 0, s, (const float*)ws, splits, M,
+                           (int)N, 1.0f, bias, (const __bf16*)residual, gamma, beta, eps, (__bf16*)out);
+      }))
+    return rc;
   prof_end(pp, s);
   return hip_status(hipGetLastError());
 }

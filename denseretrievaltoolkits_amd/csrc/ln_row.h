@@ -1,6 +1,8 @@
 // Row LayerNorm helpers shared by the encoder kernels and the GEMM's fused split-K + LayerNorm
 // finish (one wave per row, H = 64 * EPL, EPL a multiple of 4 and <= 16).
 #pragma once
+#include <type_traits>
+
 #include "drt_common.h"
 
 namespace drt {
@@ -77,6 +79,20 @@ inline unsigned ln_rows_grid(int64_t M) {
   }
   const int64_t need = (M + 3) / 4, cap = (int64_t)cus * 8;
   return (unsigned)(need < cap ? need : cap);
+}
+
+// Host dispatch on the elements per lane of a row kernel: calls f(std::integral_constant<int, EPL>)
+// for H = 64 * EPL with EPL in {4, 8, 12, 16} (the instantiations every row kernel has), so
+// `kernel<decltype(E)::value>` names the kernel inside f; DRT_EINVAL for any other H.
+template <typename F>
+inline int dispatch_epl(int64_t H, F&& f) {
+  switch (H / 64) {
+    case 4: f(std::integral_constant<int, 4>{}); return DRT_OK;
+    case 8: f(std::integral_constant<int, 8>{}); return DRT_OK;
+    case 12: f(std::integral_constant<int, 12>{}); return DRT_OK;
+    case 16: f(std::integral_constant<int, 16>{}); return DRT_OK;
+    default: return DRT_EINVAL;
+  }
 }
 
 }  // namespace drt

@@ -117,16 +117,12 @@ int drt_rmsnorm_bf16(const void* X, int64_t M, int32_t H, const float* weight, f
   if (M == 0) return DRT_OK;
   DRT_REQUIRE(X && weight && out);
   hipStream_t s = (hipStream_t)stream;
-  const __bf16* x = (const __bf16*)X;
-  __bf16* o = (__bf16*)out;
   const dim3 grid(ln_rows_grid(M));
-  switch (H / 64) {
-    case 4: hipLaunchKernelGGL(rmsnorm_bf16_kernel<4>, grid, dim3(256), 0, s, x, M, H, weight, eps, o); break;
-    case 8: hipLaunchKernelGGL(rmsnorm_bf16_kernel<8>, grid, dim3(256), 0, s, x, M, H, weight, eps, o); break;
-    case 12: hipLaunchKernelGGL(rmsnorm_bf16_kernel<12>, grid, dim3(256), 0, s, x, M, H, weight, eps, o); break;
-    case 16: hipLaunchKernelGGL(rmsnorm_bf16_kernel<16>, grid, dim3(256), 0, s, x, M, H, weight, eps, o); break;
-    default: return DRT_EINVAL;
-  }
+  if (const int rc = dispatch_epl(H, [&](auto E) {
+        hipLaunchKernelGGL(rmsnorm_bf16_kernel<decltype(E)::value>, grid, dim3(256), 0, s, (const __bf16*)X, M, H,
+                           weight, eps, (__bf16*)out);
+      }))
+    return rc;
   return hip_status(hipGetLastError());
 }
 

@@ -13,6 +13,7 @@
 //                       dropped with the mask of (p, seed, site) over the [T, F] index)
 //   t5_embedding_bwd    dshared[ids[t]] += d[t]   (no position / type table, no padding_idx)
 #include "drt_common.h"
+#include "ln_row.h"
 
 namespace drt {
 
@@ -172,19 +173,11 @@ int drt_rmsnorm_bwd_bf16(const void* dy, const void* x, const float* gamma, floa
   DRT_REQUIRE(dy && x && gamma && dx && dgamma && ws && ws_bytes >= drt_rmsnorm_bwd_workspace(M, H));
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)ws;
-  const dim3 grid(kRmsBwdBlocks);
-#define RMSB(E)                                                                                                      \
-  hipLaunchKernelGGL((rmsnorm_bwd_kernel<E>), grid, dim3(256), 0, s, (const __bf16*)dy, (const __bf16*)x, gamma, eps, \
-                     M, (int)H, (const __bf16*)dres, (__bf16*)dx, part)
-  switch (H / 64) {
-    case 4: RMSB(4); break;
-    case 8: RMSB(8); break;
-    case 12: RMSB(12); break;
-    case 16: RMSB(16); break;
-    default: return DRT_EINVAL;
-  }
-#undef RMSB
-  const int rc = hip_status(hipGetLastError());
+  int rc = dispatch_epl(H, [&](auto E) {
+    hipLaunchKernelGGL(rmsnorm_bwd_kernel<decltype(E)::value>, dim3(kRmsBwdBlocks), dim3(256), 0, s, (const __bf16*)dy,
+                       (const __bf16*)x, gamma, eps, M, (int)H, (const __bf16*)dres, (__bf16*)dx, part);
+  });
+  if (rc == DRT_OK) rc = hip_status(hipGetLastError());
   if (rc) return rc;
   // the blocks' partials in block order (drt_colsum_f32: fixed order, deterministic)
   return drt_colsum_f32(part, kRmsBwdBlocks, H, dgamma, part + (size_t)kRmsBwdBlocks * H,

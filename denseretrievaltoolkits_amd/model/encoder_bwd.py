@@ -1,5 +1,5 @@
-"""Backward building blocks of the HIP encoder tower, used by the
-training tower (model/train_tower.py).
+"""Building blocks of the HIP training towers (model/train_tower.py,
+model/t5_train_tower.py): the one place that states how they call the library.
 
 The training step of run_random_sampling.py (DRT/trainer/trainer.py:113-133) differentiates
 HF ``BertModel`` under autograd; these functions restate the gradients of its ops on the HIP
@@ -10,7 +10,10 @@ kernels for the bf16 activations the HIP forward stores:
                         directly, deterministic split over tokens, fp32 output), db = column
                         sums of dY;
 * ``layernorm_backward`` / ``gelu_backward``: thin wrappers of the C-ABI entries
-                        (include/drt.h).
+                        (include/drt.h);
+* ``linear`` / ``dropout`` / ``attention_forward`` / ``attention_backward``: the forward GEMM with
+                        its training epilogues, the hashed dropout, and the attention pair with
+                        its optional relative-position bias, dropout and bias / table gradients.
 """
 from __future__ import annotations
 
@@ -19,6 +22,8 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _native
+
+LIN_GELU = 1   # drt_linear_bf16* flag bit 0
 
 
 def _ws(nbytes: int, dev) -> Optional[torch.Tensor]:
@@ -39,6 +44,95 @@ def transpose_bf16(x: torch.Tensor, cols_pad: int = 0) -> torch.Tensor:
     _native.check(lib.drt_transpose_bf16_ld(x.data_ptr(), R, C, y.data_ptr(), R + cols_pad,
                                             _native.stream_ptr(x.device)), "drt_transpose_bf16_ld")
     return y
+
+
+def linear(x, w, out, bias=None, resid=None, flags=0, pre_out=None, drop=None):
+    """out = act(x W^T + bias) (+ resid), ``flags`` as drt_linear_bf16 takes them (bit 0 GELU, bit 3
+    ReLU); ``pre_out``: also store the pre-activation (GELU); ``drop`` = (p, seed, site):
+    out = dropout(x W^T + bias) + resid in the GEMM epilogue, which needs a bias
+    (drt_linear_bf16_ex)."""
+    lib = _native.load()
+    s = _native.stream_ptr(x.device)
+    m, k = x.shape
+    n = w.shape[0]
+    flags |= 2 if out.dtype == torch.float32 else 0   # bit 1: fp32 output, from ``out`` itself
+    nb = int(lib.drt_linear_workspace(m, n, k))
+    ws = _ws(nb, x.device)
+    if pre_out is not None or drop is not None:
+        p, seed, site = drop if drop is not None else (0.0, 0, 0)
+        _native.check(lib.drt_linear_bf16_ex(x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(resid), None, out.data_ptr(),
+                                             _ptr(pre_out), m, n, k, flags | (4 if drop is not None else 0), float(p),
+                                             seed, site, _ptr(ws), nb, s), "drt_linear_bf16_ex")
+        return out
+    _native.check(lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(resid), out.data_ptr(), m, n, k,
+                                         flags, _ptr(ws), nb, s), "drt_linear_bf16_ws")
+    return out
+
+
+def dropout(y, p, seed, site, resid=None):
+    """dropout(y) (+ resid) with the mask of (p, seed, site); on a gradient, the dropout backward."""
+    out = torch.empty_like(y)
+    _native.check(_native.load().drt_dropout_add_bf16(y.data_ptr(), _ptr(resid), y.numel(), float(p), seed, site,
+                                                      out.data_ptr(), _native.stream_ptr(y.device)),
+                  "drt_dropout_add_bf16")
+    return out
+
+
+def attention_forward(qkv, mask, B, L, heads, scale, relbias=None, drop=None):
+    """(ctx bf16 [B*L, heads*64], lse fp32 [B, heads, L], keep bits or None) of the attention over the
+    packed ``qkv``; ``relbias`` fp32 [heads, 2L-1] (T5); ``drop`` = (p, seed, site) with p > 0:
+    dropout of the probabilities, the keep mask kept as bits (B * heads * L * L / 8 bytes) for the
+    backward to read."""
+    dev = qkv.device
+    ctx = torch.empty((B * L, heads * 64), dtype=torch.bfloat16, device=dev)
+    lse = torch.empty((B, heads, L), dtype=torch.float32, device=dev)
+    p, seed, site = drop if drop is not None else (0.0, 0, 0)
+    bits = torch.empty((B, heads, L, (L + 31) // 32), dtype=torch.int32, device=dev) if p > 0 else None
+    lib = _native.load()
+    tail = (ctx.data_ptr(), lse.data_ptr(), _ptr(bits), B, L, heads, 64, float(scale), float(p), seed, site,
+            _native.stream_ptr(dev))
+    if relbias is None:
+        _native.check(lib.drt_attention_train_fwd_bits_bf16(qkv.data_ptr(), _ptr(mask), *tail),
+                      "drt_attention_train_fwd_bits_bf16")
+    else:
+        _native.check(lib.drt_attention_relbias_train_fwd_bits_bf16(qkv.data_ptr(), _ptr(mask), relbias.data_ptr(),
+                                                                    *tail), "drt_attention_relbias_train_fwd_bits_bf16")
+    return ctx, lse, bits
+
+
+def attention_backward(qkv, ctx, dctx, lse, mask, bits, B, L, heads, scale, relbias=None, drop=None,
+                       want_dbias=False):
+    """(dqkv bf16 like qkv, extra) of ``attention_forward``: extra = dtable fp32 [heads, 2L-1] with
+    ``relbias``, dbias fp32 [3 * heads * 64] (the q / k / v bias gradients, without a pass over dqkv)
+    with ``want_dbias`` (BERT; not with ``relbias``), else None."""
+    lib = _native.load()
+    dev = qkv.device
+    dqkv = torch.empty_like(qkv)
+    p, seed, site = drop if drop is not None else (0.0, 0, 0)
+    head = (qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), _ptr(mask))
+    tail = (_ptr(bits), dqkv.data_ptr(), B, L, heads, 64, float(scale), float(p), seed, site)
+    s = _native.stream_ptr(dev)
+    if relbias is not None:
+        extra = torch.empty((heads, 2 * L - 1), dtype=torch.float32, device=dev)
+        nb = int(lib.drt_attention_relbias_train_bwd_workspace(B, L, heads))
+        ws = _ws(nb, dev)
+        _native.check(lib.drt_attention_relbias_train_bwd_bf16(*head, relbias.data_ptr(), *tail, extra.data_ptr(),
+                                                               _ptr(ws), nb, s), "drt_attention_relbias_train_bwd_bf16")
+    elif want_dbias:
+        extra = torch.empty(3 * heads * 64, dtype=torch.float32, device=dev)
+        nb = int(lib.drt_attention_train_bwd_bias_workspace(B, heads, 64))
+        ws = _ws(nb, dev)
+        _native.check(lib.drt_attention_train_bwd_bias_bf16(*head, *tail, extra.data_ptr(), _ptr(ws), nb, s),
+                      "drt_attention_train_bwd_bias_bf16")
+    else:
+        extra = None
+        _native.check(lib.drt_attention_train_bwd_bits_bf16(*head, *tail, s), "drt_attention_train_bwd_bits_bf16")
+    return dqkv, extra
+
+
+def grads_out(names, grads):
+    """The autograd nodes' return for the parameters ``names``: fp32 gradients, None where absent."""
+    return tuple(grads[n].to(torch.float32) if n in grads else None for n in names)
 
 
 def colsum(x: torch.Tensor) -> torch.Tensor:
@@ -133,10 +227,9 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 def layernorm_backward(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, eps: float,
                        dres: Optional[torch.Tensor] = None, drop=None, want_sum: bool = False):
     """(dx bf16 [M, H], dgamma fp32 [H], dbeta fp32 [H]) of out = LN(x) (x = the bf16 pre-LN sums).
-    ``drop`` = (p, seed, site): also return dropout(dx) with that mask (drt_layernorm_bwd_drop_bf16)
-    as a fourth value.  ``want_sum``: also return (last) the column sums of the gradient handed
-    down -- dropout(dx), or dx -- i.e. the bias gradient of the linear below
-    (drt_layernorm_bwd_sum_bf16)."""
+    ``drop`` = (p, seed, site): also return dropout(dx) with that mask as a fourth value.
+    ``want_sum``: also return (last) the column sums of the gradient handed down -- dropout(dx), or
+    dx -- i.e. the bias gradient of the linear below."""
     lib = _native.load()
     M, H = x.shape
     dev = x.device

@@ -32,7 +32,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .. import _native
-from .encoder_bwd import _ptr, _ws, linear_backward
+from .encoder_bwd import (_ptr, _ws, attention_backward, attention_forward, dropout, grads_out, linear,
+                          linear_backward, transpose_bf16)
 from .t5_encoder import LIN_RELU, T5Shape, _relative_buckets
 
 MAX_TRAIN_SEQ = 512
@@ -69,9 +70,7 @@ class _Weights:
     """bf16 copies (and transposes) of the tower's linears for one step; fp32 norm weights / table."""
 
     def __init__(self, model, dev):
-        lib = _native.load()
         sd = dict(model.named_parameters())
-        s = _native.stream_ptr(dev)
         sh = T5Shape.from_config(model.config)
         gated = sh.act == "gated-gelu"
 
@@ -81,11 +80,7 @@ class _Weights:
         def b16(*names):
             return torch.cat([sd[n].detach() for n in names], 0).to(torch.bfloat16).contiguous()
 
-        def tr(w):   # [N, K] bf16 -> [K, N]
-            n, k = w.shape
-            y = torch.empty((k, n), dtype=torch.bfloat16, device=dev)
-            _native.check(lib.drt_transpose_bf16(w.data_ptr(), n, k, y.data_ptr(), s), "drt_transpose_bf16")
-            return y
+        tr = transpose_bf16   # [N, K] bf16 -> [K, N]
 
         self.layers = []
         for i in range(sh.layers):
@@ -116,36 +111,10 @@ class _Step:
         self.zero_bias = torch.zeros(self.D, dtype=torch.float32, device=self.dev) if drop[0] > 0 else None
 
 
-def _lin(lib, x, w, out, stream, resid=None, flags=0, drop=None, bias=None):
-    """out = x W^T (ReLU: flags) (+ resid); ``drop`` = (p, seed, site) with ``bias`` (zeros):
-    out = dropout(x W^T) + resid in the GEMM epilogue (drt_linear_bf16_ex)."""
-    m, k = x.shape
-    n = w.shape[0]
-    nb = int(lib.drt_linear_workspace(m, n, k))
-    ws = _ws(nb, x.device)
-    if drop is not None:
-        p, seed, site = drop
-        _native.check(lib.drt_linear_bf16_ex(x.data_ptr(), w.data_ptr(), bias.data_ptr(), _ptr(resid), None,
-                                             out.data_ptr(), None, m, n, k, 4, float(p), seed, site, _ptr(ws), nb,
-                                             stream), "drt_linear_bf16_ex")
-        return out
-    _native.check(lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), None, _ptr(resid), out.data_ptr(), m, n, k,
-                                         flags, _ptr(ws), nb, stream), "drt_linear_bf16_ws")
-    return out
-
-
 def _rms(lib, x, g, eps, stream):
     out = torch.empty_like(x)
     _native.check(lib.drt_rmsnorm_bf16(x.data_ptr(), x.shape[0], x.shape[1], g.data_ptr(), eps, out.data_ptr(),
                                        stream), "drt_rmsnorm_bf16")
-    return out
-
-
-def _dropout(lib, y, p, seed, site, stream):
-    """dropout(y) with the mask of (p, seed, site); on a gradient, the dropout backward."""
-    out = torch.empty_like(y)
-    _native.check(lib.drt_dropout_add_bf16(y.data_ptr(), None, y.numel(), float(p), seed, site, out.data_ptr(),
-                                           stream), "drt_dropout_add_bf16")
     return out
 
 
@@ -164,24 +133,6 @@ def rmsnorm_backward(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, eps
     return dx, dg
 
 
-def attention_relbias_backward(qkv, ctx, dctx, lse, mask, table, bits, B, L, heads, drop_p=0.0, seed=0, site=0,
-                               scale=1.0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(dqkv bf16 like qkv, dtable fp32 [heads, 2L-1]) of the attention with the bias ``table``."""
-    lib = _native.load()
-    dev = qkv.device
-    dqkv = torch.empty_like(qkv)
-    dtable = torch.empty((heads, 2 * L - 1), dtype=torch.float32, device=dev)
-    nb = int(lib.drt_attention_relbias_train_bwd_workspace(B, L, heads))
-    ws = _ws(nb, dev)
-    _native.check(lib.drt_attention_relbias_train_bwd_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
-                                                           lse.data_ptr(), _ptr(mask), table.data_ptr(), _ptr(bits),
-                                                           dqkv.data_ptr(), B, L, heads, 64, float(scale),
-                                                           float(drop_p), seed, site, dtable.data_ptr(), _ptr(ws), nb,
-                                                           _native.stream_ptr(dev)),
-                  "drt_attention_relbias_train_bwd_bf16")
-    return dqkv, dtable
-
-
 def embed_forward(st: _Step):
     lib = _native.load()
     s = _native.stream_ptr(st.dev)
@@ -189,7 +140,7 @@ def embed_forward(st: _Step):
     _native.check(lib.drt_t5_embed_bf16(st.ids.data_ptr(), st.B, st.L, st.W.word.data_ptr(), st.D, h.data_ptr(), s),
                   "drt_t5_embed_bf16")
     p, seed = st.drop
-    return _dropout(lib, h, p, seed, SITE_EMBED, s) if p > 0 else h
+    return dropout(h, p, seed, SITE_EMBED) if p > 0 else h
 
 
 def embed_backward(st: _Step, d) -> torch.Tensor:
@@ -197,7 +148,7 @@ def embed_backward(st: _Step, d) -> torch.Tensor:
     s = _native.stream_ptr(st.dev)
     p, seed = st.drop
     if p > 0:
-        d = _dropout(lib, d, p, seed, SITE_EMBED, s)
+        d = dropout(d, p, seed, SITE_EMBED)
     dword = torch.zeros_like(st.W.word)
     _native.check(lib.drt_t5_embedding_bwd(st.ids.data_ptr(), d.data_ptr(), st.B, st.L, st.D, int(dword.shape[0]),
                                            dword.data_ptr(), s), "drt_t5_embedding_bwd")
@@ -218,28 +169,20 @@ def block_forward(st: _Step, i: int, h, table):
         return torch.empty((T, n), dtype=torch.bfloat16, device=dev)
 
     x0 = _rms(lib, h, ly["g0"], sh.eps, s)
-    qkv = _lin(lib, x0, ly["wqkv"], buf(3 * st.I), s)
-    ctx = buf(st.I)
-    lse = torch.empty((B, sh.heads, L), dtype=torch.float32, device=dev)
-    bits = torch.empty((B, sh.heads, L, (L + 31) // 32), dtype=torch.int32, device=dev) if p > 0 else None
-    _native.check(lib.drt_attention_relbias_train_fwd_bits_bf16(qkv.data_ptr(), _ptr(st.mask), table.data_ptr(),
-                                                                ctx.data_ptr(), lse.data_ptr(), _ptr(bits), B, L,
-                                                                sh.heads, sh.d_kv, 1.0, float(p), seed, s_att, s),
-                  "drt_attention_relbias_train_fwd_bits_bf16")
+    qkv = linear(x0, ly["wqkv"], buf(3 * st.I))
+    ctx, lse, bits = attention_forward(qkv, st.mask, B, L, sh.heads, 1.0, relbias=table, drop=(p, seed, s_att))
     # h2 = dropout(ctx Wo^T) + h, the dropout in the GEMM epilogue
-    h2 = _lin(lib, ctx, ly["wo"], buf(st.D), s, resid=h, drop=(p, seed, s_out1) if p > 0 else None,
-              bias=st.zero_bias)
+    h2 = linear(ctx, ly["wo"], buf(st.D), bias=st.zero_bias, resid=h, drop=(p, seed, s_out1) if p > 0 else None)
     x1 = _rms(lib, h2, ly["g1"], sh.eps, s)
     if st.gated:
-        pre = _lin(lib, x1, ly["wi"], buf(2 * st.F), s)
+        pre = linear(x1, ly["wi"], buf(2 * st.F))
         f = buf(st.F)
         _native.check(lib.drt_gated_gelu_new_bf16(pre.data_ptr(), T, st.F, f.data_ptr(), s), "drt_gated_gelu_new_bf16")
     else:
         pre = None
-        f = _lin(lib, x1, ly["wi"], buf(st.F), s, flags=LIN_RELU)
-    fd = _dropout(lib, f, p, seed, s_inner, s) if p > 0 else f   # what wo reads
-    out = _lin(lib, fd, ly["wf"], buf(st.D), s, resid=h2, drop=(p, seed, s_out2) if p > 0 else None,
-               bias=st.zero_bias)
+        f = linear(x1, ly["wi"], buf(st.F), flags=LIN_RELU)
+    fd = dropout(f, p, seed, s_inner) if p > 0 else f   # what wo reads
+    out = linear(fd, ly["wf"], buf(st.D), bias=st.zero_bias, resid=h2, drop=(p, seed, s_out2) if p > 0 else None)
     # the gated backward reads its pre-activations; ReLU's only the sign of f, and where the inner
     # dropout zeroed fd the gradient is dropped anyway: fd serves
     return out, (h, x0, qkv, ctx, lse, bits, h2, x1, pre, fd)
@@ -256,7 +199,7 @@ def block_backward(st: _Step, i: int, saved, table, d):
     p, seed = st.drop
     s_att, s_out1, s_inner, s_out2 = t5_dropout_sites(i)
     # out = h2 + dropout(fd Wf^T)
-    dy2 = _dropout(lib, d, p, seed, s_out2, s) if p > 0 else d
+    dy2 = dropout(d, p, seed, s_out2) if p > 0 else d
     dfd, dwf, _ = linear_backward(dy2, fd, ly["wf_t"], want_db=False)
     if st.gated:
         dpre = torch.empty_like(pre)
@@ -269,10 +212,10 @@ def block_backward(st: _Step, i: int, saved, table, d):
     dx1, dwi, _ = linear_backward(dpre, x1, ly["wi_t"], want_db=False)
     dh2, dg1 = rmsnorm_backward(dx1, h2, ly["g1"], sh.eps, dres=d)
     # h2 = h + dropout(ctx Wo^T)
-    dy1 = _dropout(lib, dh2, p, seed, s_out1, s) if p > 0 else dh2
+    dy1 = dropout(dh2, p, seed, s_out1) if p > 0 else dh2
     dctx, dwo, _ = linear_backward(dy1, ctx, ly["wo_t"], want_db=False)
-    dqkv, dtable = attention_relbias_backward(qkv, ctx, dctx, lse, st.mask, table, bits, st.B, st.L, sh.heads,
-                                              drop_p=p, seed=seed, site=s_att)
+    dqkv, dtable = attention_backward(qkv, ctx, dctx, lse, st.mask, bits, st.B, st.L, sh.heads, 1.0, relbias=table,
+                                      drop=(p, seed, s_att))
     dx0, dwqkv, _ = linear_backward(dqkv, x0, ly["wqkv_t"], want_db=False)
     d_in, dg0 = rmsnorm_backward(dx0, h, ly["g0"], sh.eps, dres=dh2)
     a = f"encoder.block.{i}.layer.0."
@@ -291,19 +234,14 @@ def final_forward(st: _Step, h):
     s = _native.stream_ptr(st.dev)
     p, seed = st.drop
     y = _rms(lib, h, st.W.final_g, st.sh.eps, s)
-    return _dropout(lib, y, p, seed, SITE_FINAL, s) if p > 0 else y
+    return dropout(y, p, seed, SITE_FINAL) if p > 0 else y
 
 
 def final_backward(st: _Step, h, d):
-    lib = _native.load()
     p, seed = st.drop
     if p > 0:
-        d = _dropout(lib, d, p, seed, SITE_FINAL, _native.stream_ptr(st.dev))
+        d = dropout(d, p, seed, SITE_FINAL)
     return rmsnorm_backward(d, h, st.W.final_g, st.sh.eps)
-
-
-def _grads_out(names, grads):
-    return tuple(grads[n].to(torch.float32) if n in grads else None for n in names)
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -328,7 +266,7 @@ class _BlockFn(torch.autograd.Function):
     def backward(ctx, d):
         d_in, dtable, grads = block_backward(ctx.st, ctx.i, ctx.saved_acts, ctx.table, d.contiguous())
         ctx.saved_acts = None
-        return (d_in, dtable, None, None, None) + _grads_out(ctx.names, grads)
+        return (d_in, dtable, None, None, None) + grads_out(ctx.names, grads)
 
 
 class _FinalFn(torch.autograd.Function):

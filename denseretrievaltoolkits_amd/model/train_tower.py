@@ -31,7 +31,8 @@ import torch
 
 from .. import _native
 from .encoder import BertShape, _check_supported
-from .encoder_bwd import _ptr, layernorm_backward, linear_backward
+from .encoder_bwd import (LIN_GELU, _ptr, attention_backward, attention_forward, dropout, grads_out,
+                          layernorm_backward, linear, linear_backward, transpose_bf16)
 
 MAX_TRAIN_SEQ = 512
 
@@ -52,21 +53,15 @@ class _Weights:
     """bf16 copies (and transposes) of the tower's linears for one step; fp32 LN / bias / tables."""
 
     def __init__(self, model, dev):
-        lib = _native.load()
         sd = dict(model.named_parameters())
         self.names = list(sd.keys())
         self.sd = sd
         self.layers = []
-        s = _native.stream_ptr(dev)
 
         def b16(t):
             return t.detach().to(torch.bfloat16).contiguous()
 
-        def tr(w):   # [N, K] bf16 -> [K, N]
-            n, k = w.shape
-            y = torch.empty((k, n), dtype=torch.bfloat16, device=dev)
-            _native.check(lib.drt_transpose_bf16(w.data_ptr(), n, k, y.data_ptr(), s), "drt_transpose_bf16")
-            return y
+        tr = transpose_bf16   # [N, K] bf16 -> [K, N]
 
         nl = model.config.num_hidden_layers
         for i in range(nl):
@@ -94,36 +89,10 @@ class _Weights:
         self.emb_b = sd[e + "LayerNorm.bias"].detach().float().contiguous()
 
 
-def _lin(lib, x, w, b, out, resid=None, gelu=False, stream=None, pre_out=None, drop=None):
-    """out = x W^T + b (GELU) (+ resid); ``pre_out``: also store the pre-activation (GELU);
-    ``drop`` = (p, seed, site): out = dropout(x W^T + b) + resid (drt_linear_bf16_ex epilogues)."""
-    m, k = x.shape
-    n = w.shape[0]
-    flags = (1 if gelu else 0) | (2 if out.dtype == torch.float32 else 0)
-    nb = int(lib.drt_linear_workspace(m, n, k))
-    ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device) if nb else None
-    if pre_out is not None or drop is not None:
-        p, seed, site = drop if drop is not None else (0.0, 0, 0)
-        _native.check(lib.drt_linear_bf16_ex(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(resid), None, out.data_ptr(),
-                                             _ptr(pre_out), m, n, k, flags | (4 if drop is not None else 0), float(p),
-                                             seed, site, _ptr(ws), nb, stream), "drt_linear_bf16_ex")
-        return out
-    _native.check(lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(resid), out.data_ptr(), m, n, k,
-                                         flags, _ptr(ws), nb, stream), "drt_linear_bf16_ws")
-    return out
-
-
 def _layernorm(lib, x, g, b, eps, stream):
     out = torch.empty_like(x)
     _native.check(lib.drt_layernorm_bf16(x.data_ptr(), x.shape[0], x.shape[1], g.data_ptr(), b.data_ptr(), eps,
                                          out.data_ptr(), stream), "drt_layernorm_bf16")
-    return out
-
-
-def _dropout(lib, y, p, seed, site, stream, resid=None):
-    out = torch.empty_like(y)
-    _native.check(lib.drt_dropout_add_bf16(y.data_ptr(), _ptr(resid), y.numel(), float(p), seed, site,
-                                           out.data_ptr(), stream), "drt_dropout_add_bf16")
     return out
 
 
@@ -159,7 +128,7 @@ def embed_forward(st: _Step):
                                        h.data_ptr(), emb_pre.data_ptr(), s), "drt_embed_ln_pre")
     ph, _, seed = st.drop
     if ph > 0:
-        h = _dropout(lib, h, ph, seed, 0, s)
+        h = dropout(h, ph, seed, 0)
     return h, emb_pre
 
 
@@ -169,16 +138,15 @@ def embed_backward(st: _Step, emb_pre, d) -> Dict[str, torch.Tensor]:
     W = st.W
     ph, _, seed = st.drop
     if ph > 0:
-        d = _dropout(lib, d, ph, seed, 0, s)
+        d = dropout(d, ph, seed, 0)
     demb, dge, dbe = layernorm_backward(d, emb_pre, W.emb_g, st.eps)
     dword = torch.zeros_like(W.word)
     dpos = torch.zeros_like(W.pos)
     dtype = torch.zeros_like(W.type)
     pad = st.model.embeddings.word_embeddings.padding_idx
-    _native.check(lib.drt_embedding_bwd_types(st.ids.data_ptr(), _ptr(st.types), int(W.type.shape[0]),
-                                              demb.data_ptr(), st.B, st.L, st.H, -1 if pad is None else int(pad),
-                                              dword.data_ptr(), dpos.data_ptr(), dtype.data_ptr(), s),
-                  "drt_embedding_bwd_types")
+    _native.check(lib.drt_embedding_bwd(st.ids.data_ptr(), _ptr(st.types), int(W.type.shape[0]), demb.data_ptr(),
+                                        st.B, st.L, st.H, -1 if pad is None else int(pad), dword.data_ptr(),
+                                        dpos.data_ptr(), dtype.data_ptr(), s), "drt_embedding_bwd")
     e = "embeddings."
     return {e + "word_embeddings.weight": dword, e + "position_embeddings.weight": dpos,
             e + "token_type_embeddings.weight": dtype, e + "LayerNorm.weight": dge, e + "LayerNorm.bias": dbe}
@@ -194,33 +162,22 @@ def layer_forward(st: _Step, i: int, h):
     T = B * L
     ph, pa, seed = st.drop
     s_att, s_out1, s_out2 = dropout_sites(i)
-    qkv = _lin(lib, h, ly["wqkv"], ly["bqkv"], torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev), stream=s)
-    ctx = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
-    lse = torch.empty((B, heads, L), dtype=torch.float32, device=dev)
-    # attention-dropout keep mask as bits (B * heads * L * L / 8 bytes): the backward reads it
-    bits = torch.empty((B, heads, L, (L + 31) // 32), dtype=torch.int32, device=dev) if pa > 0 else None
-    _native.check(lib.drt_attention_train_fwd_bits_bf16(qkv.data_ptr(), _ptr(st.mask), ctx.data_ptr(),
-                                                        lse.data_ptr(), _ptr(bits), B, L, heads, H // heads, st.scale,
-                                                        float(pa), seed, s_att, s),
-                  "drt_attention_train_fwd_bits_bf16")
+    qkv = linear(h, ly["wqkv"], torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev), bias=ly["bqkv"])
+    ctx, lse, bits = attention_forward(qkv, st.mask, B, L, heads, st.scale, drop=(pa, seed, s_att))
     # x1 = dropout(ctx Wo^T + bo) + h, dropout in the GEMM epilogue
-    x1 = _lin(lib, ctx, ly["wo"], ly["bo"], torch.empty_like(h), resid=h, stream=s,
-              drop=(ph, seed, s_out1) if ph > 0 else None)
+    x1 = linear(ctx, ly["wo"], torch.empty_like(h), bias=ly["bo"], resid=h, drop=(ph, seed, s_out1) if ph > 0 else None)
     h1 = _layernorm(lib, x1, ly["g1"], ly["b1"], st.eps, s)
     # f = GELU(fpre), fpre = h1 Wi^T + bi: both from the one GEMM epilogue
     fpre = torch.empty((T, ly["wi"].shape[0]), dtype=torch.bfloat16, device=dev)
-    f = _lin(lib, h1, ly["wi"], ly["bi"], torch.empty_like(fpre), gelu=True, stream=s, pre_out=fpre)
+    f = linear(h1, ly["wi"], torch.empty_like(fpre), bias=ly["bi"], flags=LIN_GELU, pre_out=fpre)
     # x2 = dropout(f Wf^T + bf) + h1
-    x2 = _lin(lib, f, ly["wf"], ly["bf"], torch.empty_like(h), resid=h1, stream=s,
-              drop=(ph, seed, s_out2) if ph > 0 else None)
+    x2 = linear(f, ly["wf"], torch.empty_like(h), bias=ly["bf"], resid=h1, drop=(ph, seed, s_out2) if ph > 0 else None)
     h2 = _layernorm(lib, x2, ly["g2"], ly["b2"], st.eps, s)
     return h2, (h, qkv, ctx, lse, bits, x1, h1, fpre, f, x2)
 
 
 def layer_backward(st: _Step, i: int, saved, d) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """d h_in and the fp32 gradients of layer i's parameters (HF names) for d h_out."""
-    lib = _native.load()
-    s = _native.stream_ptr(st.dev)
     h, qkv, ctx, lse, bits, x1, h1, fpre, f, x2 = saved
     ly = st.W.layers[i]
     H, heads, eps = st.H, st.heads, st.eps
@@ -245,17 +202,10 @@ def layer_backward(st: _Step, i: int, saved, d) -> Tuple[torch.Tensor, Dict[str,
         dx1, dg1, db1, sum1 = layernorm_backward(dh1, x1, ly["g1"], eps, want_sum=True)
         dy1 = dx1
     dctx, dwo, dbo = linear_backward(dy1, ctx, ly["wo_t"], db=sum1)
-    dqkv = torch.empty_like(qkv)
     # the attention backward also leaves per-sequence column sums of dQKV: the q / k / v bias
     # gradients without a pass over dQKV
-    dbqkv = torch.empty(3 * H, dtype=torch.float32, device=st.dev)
-    nb = int(lib.drt_attention_train_bwd_bias_workspace(st.B, heads, H // heads))
-    ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=st.dev)
-    _native.check(lib.drt_attention_train_bwd_bias_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
-                                                        lse.data_ptr(), _ptr(st.mask), _ptr(bits), dqkv.data_ptr(),
-                                                        st.B, st.L, heads, H // heads, st.scale, float(pa), seed,
-                                                        s_att, dbqkv.data_ptr(), ws.data_ptr(), nb, s),
-                  "drt_attention_train_bwd_bias_bf16")
+    dqkv, dbqkv = attention_backward(qkv, ctx, dctx, lse, st.mask, bits, st.B, st.L, heads, st.scale,
+                                     drop=(pa, seed, s_att), want_dbias=True)
     d_in, dwqkv, dbqkv = linear_backward(dqkv, h, ly["wqkv_t"], resid=dx1, db=dbqkv)
     grads = {}
     grads[p + "output.LayerNorm.weight"], grads[p + "output.LayerNorm.bias"] = dg2, db2
@@ -274,8 +224,6 @@ def layer_backward(st: _Step, i: int, saved, d) -> Tuple[torch.Tensor, Dict[str,
 # is done, and DDP's gradient all-reduce of layer i overlaps the backward of layers i-1 .. 0
 # (trainer.py:47-63 wraps the model in DDP).  The activation between nodes is the bf16 hidden
 # state; all nodes of one pass share a _Step (weights snapshot, ids, mask, dropout seed).
-def _grads_out(names, grads):
-    return tuple(grads[n].to(torch.float32) if n in grads else None for n in names)
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -289,7 +237,7 @@ class _EmbedFn(torch.autograd.Function):
     def backward(ctx, d):
         grads = embed_backward(ctx.st, ctx.emb_pre, d.contiguous())
         ctx.emb_pre = None
-        return (None, None, None) + _grads_out(ctx.names, grads)
+        return (None, None, None) + grads_out(ctx.names, grads)
 
 
 class _LayerFn(torch.autograd.Function):
@@ -303,7 +251,7 @@ class _LayerFn(torch.autograd.Function):
     def backward(ctx, d):
         d_in, grads = layer_backward(ctx.st, ctx.i, ctx.saved_acts, d.contiguous())
         ctx.saved_acts = None
-        return (d_in, None, None, None) + _grads_out(ctx.names, grads)
+        return (d_in, None, None, None) + grads_out(ctx.names, grads)
 
 
 def _param_groups(model):

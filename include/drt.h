@@ -431,15 +431,11 @@ size_t drt_layernorm_bwd_workspace(int64_t M, int32_t H);
 int drt_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M,
                            int32_t H, const void* dres, void* dx, float* dgamma, float* dbeta,
                            void* ws, size_t ws_bytes, void* stream);
-/* The same, also writing dx_drop = dropout(dx) with drt_dropout_add_bf16's mask of
- * (drop_p, seed, site) at the flat index m * H + h (the gradient of a linear whose output was
- * dropped before this LayerNorm's residual add; replaces a separate dropout pass).          */
-int drt_layernorm_bwd_drop_bf16(const void* dy, const void* x, const float* gamma, float eps,
-                                int64_t M, int32_t H, const void* dres, void* dx, void* dx_drop,
-                                float drop_p, uint64_t seed, uint64_t site, float* dgamma,
-                                float* dbeta, void* ws, size_t ws_bytes, void* stream);
-/* The same, also writing dsum [H] fp32 = the column sums of the gradient it hands down (dx_drop,
- * or dx when dx_drop is NULL): the bias gradient of the linear feeding this LayerNorm
+/* drt_layernorm_bwd_sum_bf16: the same with two optional outputs (NULL = without): dx_drop =
+ * dropout(dx) with drt_dropout_add_bf16's mask of (drop_p, seed, site) at the flat index m * H + h
+ * (the gradient of a linear whose output was dropped before this LayerNorm's residual add; replaces
+ * a separate dropout pass), and dsum [H] fp32 = the column sums of the gradient it hands down
+ * (dx_drop, or dx when dx_drop is NULL): the bias gradient of the linear feeding this LayerNorm
  * (BertSelfOutput / BertOutput dense.bias) without a separate pass over that gradient.   */
 int drt_layernorm_bwd_sum_bf16(const void* dy, const void* x, const float* gamma, float eps,
                                int64_t M, int32_t H, const void* dres, void* dx, void* dx_drop,
@@ -469,47 +465,36 @@ int drt_linear_wgrad_bf16(const void* dY, const void* X, float* dW, int64_t T, i
 /* drt_embed_ln_pre: drt_embed_ln that also writes the bf16 pre-LN sum (word + type + pos).
  * drt_gelu_bf16: y = GELU(x) elementwise (erf form).
  * drt_embedding_bwd: scatter-add of d [B*L, H] (gradient of the pre-LN embedding sum) into
- *   dword [V,H], dpos [P,H], dtype [types,H] fp32 (caller zeroes them: word rows by atomics,
- *   position rows by chunked column sums, token type 0 from the position sums when
- *   type_ids is NULL); tokens equal to padding_idx (nn.Embedding(padding_idx), -1 = none)
- *   add nothing to dword.                                                                   */
+ *   dword [V,H], dpos [P,H], dtype [ntypes,H] fp32 (caller zeroes them: word rows by atomics,
+ *   position rows by chunked column sums, the type rows by per-type column sums over token
+ *   chunks -- ntypes = type_vocab_size <= 4 when type_ids is given, BERT: 2 -- or token type 0
+ *   from the position sums when type_ids is NULL); tokens equal to padding_idx
+ *   (nn.Embedding(padding_idx), -1 = none) add nothing to dword.                            */
 int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L,
                      const float* word_emb, const float* pos_emb, const float* type_emb,
                      const float* gamma, const float* beta, float eps, int32_t H, void* out, void* pre,
                      void* stream);
 int drt_gelu_bf16(const void* x, int64_t n, void* y, void* stream);
-int drt_embedding_bwd(const int64_t* ids, const int64_t* type_ids, const void* d, int64_t B, int64_t L,
-                      int32_t H, int64_t padding_idx, float* dword, float* dpos, float* dtype,
-                      void* stream);
-/* drt_embedding_bwd with the token-type table's row count (type_vocab_size <= 4 when type_ids is
- * given; BERT: 2): the type rows' gradients are per-type column sums over token chunks (drt_embedding_bwd
- * assumes 2 rows).                                                                            */
-int drt_embedding_bwd_types(const int64_t* ids, const int64_t* type_ids, int32_t ntypes, const void* d,
-                            int64_t B, int64_t L, int32_t H, int64_t padding_idx, float* dword, float* dpos,
-                            float* dtype, void* stream);
+int drt_embedding_bwd(const int64_t* ids, const int64_t* type_ids, int32_t ntypes, const void* d,
+                      int64_t B, int64_t L, int32_t H, int64_t padding_idx, float* dword, float* dpos,
+                      float* dtype, void* stream);
 int drt_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                            const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads,
                            int32_t head_dim, float scale, void* stream);
 /* Training dropout (HF train mode, modeling_bert.py:107,195,296,348): keep element i of a
  * site iff drop_hash24(seed, site, i) >= p 2^24 (csrc/drt_common.h), kept values / (1 - p).
- * drt_attention_train_fwd_bf16 / _bwd_bf16: attention with dropout of the probabilities
- *   (element index ((b*heads + head)*L + q)*L + key); p = 0 is the plain forward / backward.
  * drt_dropout_add_bf16: out = dropout(y) + resid (resid may be NULL) over n elements; the
  *   same call on a gradient with resid = NULL is the dropout backward.                      */
-int drt_attention_train_fwd_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B,
-                                 int64_t L, int32_t heads, int32_t head_dim, float scale, float drop_p,
-                                 uint64_t seed, uint64_t site, void* stream);
-int drt_attention_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                 const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads,
-                                 int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
-                                 void* stream);
 int drt_dropout_add_bf16(const void* y, const void* resid, int64_t n, float p, uint64_t seed, uint64_t site,
                          void* out, void* stream);
-/* The training attention pair with the dropout keep mask kept as bits: the forward writes
- * drop_bits [B][heads][L][ceil(L / 32)] u32 (bit key & 31 of word (query, key >> 5); only when
- * drop_p > 0 and drop_bits != NULL), the backward reads them instead of regenerating the hash
- * twice per (query, key).  Same masks, same results as the hash-regenerating pair.  For
- * L > 160 with drop_p > 0 the backward requires drop_bits (DRT_EINVAL without).              */
+/* The training attention pair: drt_attention_fwd_lse_bf16 / drt_attention_bwd_bf16 with dropout of
+ * the probabilities (drop_p, seed, site; the keep of (b, head, q, key) is drawn from the pairwise
+ * hash of csrc/drt_common.h, attn_row_key / attn_keep; p = 0 is the plain forward / backward) and
+ * the keep mask kept as bits: the forward writes drop_bits [B][heads][L][ceil(L / 32)] u32 (bit
+ * key & 31 of word (query, key >> 5); only when drop_p > 0 and drop_bits != NULL), the backward
+ * reads them instead of regenerating the hash twice per (query, key); NULL drop_bits = regenerate
+ * (same masks, same results).  For L > 160 with drop_p > 0 the backward requires drop_bits
+ * (DRT_EINVAL without).                                                                        */
 int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse,
                                       uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads,
                                       int32_t head_dim, float scale, float drop_p, uint64_t seed,
