@@ -94,14 +94,11 @@ _SIGNATURES = [
     ("drt_linear_ln_bf16_ws", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_i64, c_i64,
                                       c_vp, c_sz, c_vp]),
     ("drt_layernorm_f32_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
-    ("drt_attention_fwd_lse_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     ("drt_layernorm_bwd_workspace", c_sz, [c_i64, c_i32]),
-    ("drt_layernorm_bwd_sum_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_f32, c_u64,
-                                           c_u64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    ("drt_layernorm_backward_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_f32, c_u64,
+                                            c_u64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("drt_linear_bf16_ex", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_u64,
                                    c_u64, c_vp, c_sz, c_vp]),
-    ("drt_layernorm_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
-                                       c_vp]),
     ("drt_colsum_workspace", c_sz, [c_i64, c_i64]),
     ("drt_colsum_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
     ("drt_colsum_f32", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
@@ -117,28 +114,37 @@ _SIGNATURES = [
     ("drt_gelu_bf16", c_i32, [c_vp, c_i64, c_vp, c_vp]),
     ("drt_embedding_bwd", c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     ("drt_dropout_add_bf16", c_i32, [c_vp, c_vp, c_i64, c_f32, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp]),
+    ("drt_attention_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32,
+                                           c_f32, c_u64, c_u64, c_vp]),
+    ("drt_attention_backward_workspace", c_sz, [c_i64, c_i64, c_i32, c_i32, c_i32]),
+    ("drt_attention_backward_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32,
+                                            c_f32, c_f32, c_u64, c_u64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    # the earlier names of the attention pair and the LayerNorm backward (drt.h): argument subsets
+    ("drt_attention_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
+    ("drt_attention_fwd_lse_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     ("drt_attention_train_fwd_bits_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32,
                                                   c_f32, c_u64, c_u64, c_vp]),
+    ("drt_attention_relbias_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
+    ("drt_attention_relbias_train_fwd_bits_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32,
+                                                          c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
+    ("drt_attention_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     ("drt_attention_train_bwd_bits_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32,
                                                   c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
     ("drt_attention_train_bwd_bias_workspace", c_sz, [c_i64, c_i32, c_i32]),
     ("drt_attention_train_bwd_bias_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32,
                                                   c_i32, c_f32, c_f32, c_u64, c_u64, c_vp, c_vp, c_sz, c_vp]),
-    ("drt_attention_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
-    ("drt_layernorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
-    ("drt_attention_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
-    ("drt_pool_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
-    ("drt_l2_normalize_f32", c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
-    ("drt_t5_embed_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
-    ("drt_rmsnorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
-    ("drt_attention_relbias_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
-    ("drt_gated_gelu_new_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
-    ("drt_attention_relbias_train_fwd_bits_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32,
-                                                          c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
     ("drt_attention_relbias_train_bwd_workspace", c_sz, [c_i64, c_i64, c_i32]),
     ("drt_attention_relbias_train_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                                      c_i32, c_i32, c_f32, c_f32, c_u64, c_u64, c_vp, c_vp, c_sz,
                                                      c_vp]),
+    ("drt_layernorm_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                       c_vp]),
+    ("drt_layernorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    ("drt_pool_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    ("drt_l2_normalize_f32", c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
+    ("drt_t5_embed_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    ("drt_rmsnorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
+    ("drt_gated_gelu_new_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),
     ("drt_rmsnorm_bwd_workspace", c_sz, [c_i64, c_i32]),
     ("drt_rmsnorm_bwd_bf16", c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     ("drt_gated_gelu_new_bwd_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_f32, c_u64, c_u64, c_vp, c_vp]),

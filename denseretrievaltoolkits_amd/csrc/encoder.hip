@@ -10,7 +10,7 @@
 //                   tiles; S^T = K Q^T keeps each query's scores lane-local and
 //                   the S^T accumulator feeds the P.V MFMA directly as its B
 //                   operand (no LDS round trip for P); the RB instantiations add T5's
-//                   relative-position bias to the scores (drt_attention_relbias_bf16)
+//                   relative-position bias to the scores (drt_attention_forward_bf16, relbias)
 //   pool            first / masked-mean / masked-max pooling (utils.py:233-240)
 //   l2norm          F.normalize(reps, dim=1) (biencoder.py:149-150)
 #include "drt_common.h"
@@ -579,46 +579,6 @@ __global__ __launch_bounds__(256) void l2norm_kernel(float* x, int64_t B, int H,
   }
 }
 
-// The host driver behind the five attention forward entries: every instantiation of
-// attention_fwd_kernel.  rb (the relbias entries; T5Attention, modeling_t5.py: scores = q k^T +
-// position_bias, no 1 / sqrt(d) -- the caller passes scale = 1) selects the RB kernels, drop_p > 0
-// the DROP ones; lse and drop_bits are written when given.  At drop_p = 0 the training forward
-// runs the inference kernels: the same ctx bits.
-static int attention_fwd(const void* qkv, const int64_t* mask, bool rb, const float* relbias, void* ctx, float* lse,
-                         uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
-                         float drop_p, uint64_t seed, uint64_t site, void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  if (B == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx && (!rb || relbias));
-  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, lse, drop_p, seed, site,
-             drop_bits, relbias};
-  using Kernel = void (*)(AttnArgs);
-#define DRT_AF_ROW(NB)                                                          \
-  {{attention_fwd_kernel<NB, false, false>, attention_fwd_kernel<NB, false, true>}, \
-   {attention_fwd_kernel<NB, true, false>, attention_fwd_kernel<NB, true, true>}}
-  // [NB][drop][rb]; NB = 0: 161 <= L <= 512 (the backward's streamed kernels)
-  static constexpr Kernel kernels[6][2][2] = {DRT_AF_ROW(0), DRT_AF_ROW(1), DRT_AF_ROW(2),
-                                              DRT_AF_ROW(3), DRT_AF_ROW(4), DRT_AF_ROW(5)};
-#undef DRT_AF_ROW
-  const bool drop = drop_p > 0.0f;
-  const int Lp = ((int)L + 31) & ~31;
-  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (rb ? (size_t)Lp * 8 : 0);
-  static bool attr_set = false;
-  if (!attr_set) {   // L > 224 stages more than the default 64 KiB
-    for (const auto& by_drop : kernels)
-      for (const auto& by_rb : by_drop)
-        for (const Kernel k : by_rb)
-          DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  void* args[] = {&a};
-  hipLaunchKernel((const void*)kernels[nb][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
-                  (hipStream_t)stream);
-  return hip_status(hipGetLastError());
-}
-
 }  // namespace drt
 
 using namespace drt;
@@ -709,39 +669,80 @@ int drt_layernorm_bf16(const void* X, int64_t M, int32_t H, const float* gamma, 
   return hip_status(hipGetLastError());
 }
 
+// The attention forward (contract: drt.h): every instantiation of attention_fwd_kernel.  relbias
+// (T5Attention, modeling_t5.py: scores = q k^T + position_bias, no 1 / sqrt(d) -- the caller
+// passes scale = 1) selects the RB kernels, drop_p > 0 the DROP ones; lse and drop_bits are
+// written when given.  At drop_p = 0 the training forward runs the inference kernels: the same
+// ctx bits.
+int drt_attention_forward_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx, float* lse,
+                               uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
+                               float drop_p, uint64_t seed, uint64_t site, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  if (B == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx);
+  AttnArgs a{(const __bf16*)qkv, mask, (__bf16*)ctx, B, L, heads, heads * head_dim, scale, lse, drop_p, seed, site,
+             drop_bits, relbias};
+  using Kernel = void (*)(AttnArgs);
+#define DRT_AF_ROW(NB)                                                          \
+  {{attention_fwd_kernel<NB, false, false>, attention_fwd_kernel<NB, false, true>}, \
+   {attention_fwd_kernel<NB, true, false>, attention_fwd_kernel<NB, true, true>}}
+  // [NB][drop][rb]; NB = 0: 161 <= L <= 512 (the backward's streamed kernels)
+  static constexpr Kernel kernels[6][2][2] = {DRT_AF_ROW(0), DRT_AF_ROW(1), DRT_AF_ROW(2),
+                                              DRT_AF_ROW(3), DRT_AF_ROW(4), DRT_AF_ROW(5)};
+#undef DRT_AF_ROW
+  const bool drop = drop_p > 0.0f, rb = relbias != nullptr;
+  const int Lp = ((int)L + 31) & ~31;
+  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (rb ? (size_t)Lp * 8 : 0);
+  static bool attr_set = false;
+  if (!attr_set) {   // L > 224 stages more than the default 64 KiB
+    for (const auto& by_drop : kernels)
+      for (const auto& by_rb : by_drop)
+        for (const Kernel k : by_rb)
+          DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  void* args[] = {&a};
+  hipLaunchKernel((const void*)kernels[nb][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
+                  (hipStream_t)stream);
+  return hip_status(hipGetLastError());
+}
+
+// The earlier names (drt.h, "Earlier attention names"): argument subsets of the entry above.
 int drt_attention_bf16(const void* qkv, const int64_t* mask, void* ctx, int64_t B, int64_t L, int32_t heads,
                        int32_t head_dim, float scale, void* stream) {
-  return attention_fwd(qkv, mask, false, nullptr, ctx, nullptr, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
+  return drt_attention_forward_bf16(qkv, mask, nullptr, ctx, nullptr, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0,
+                                    stream);
 }
 
 int drt_attention_fwd_lse_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B, int64_t L,
                                int32_t heads, int32_t head_dim, float scale, void* stream) {
-  return attention_fwd(qkv, mask, false, nullptr, ctx, lse, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
+  return drt_attention_forward_bf16(qkv, mask, nullptr, ctx, lse, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0,
+                                    stream);
 }
 
-// The training forward: lse, attention-probability dropout and (when drop_p > 0 and drop_bits !=
-// NULL) the keep mask as bits, [B][heads][L][ceil(L / 32)] u32, bit (key & 31) of word
-// (query, key >> 5); drt_attention_train_bwd_bits_bf16 reads it instead of regenerating the hash.
 int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse,
                                       uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
                                       float scale, float drop_p, uint64_t seed, uint64_t site, void* stream) {
-  return attention_fwd(qkv, mask, false, nullptr, ctx, lse, drop_bits, B, L, heads, head_dim, scale, drop_p, seed, site,
-                       stream);
+  return drt_attention_forward_bf16(qkv, mask, nullptr, ctx, lse, drop_bits, B, L, heads, head_dim, scale, drop_p, seed,
+                                    site, stream);
 }
 
-// The same two with a relative-position bias: relbias fp32 [heads][2 L - 1], entry
-// (head, key - query + L - 1).
 int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx, int64_t B,
                                int64_t L, int32_t heads, int32_t head_dim, float scale, void* stream) {
-  return attention_fwd(qkv, mask, true, relbias, ctx, nullptr, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0, stream);
+  DRT_REQUIRE(relbias || B == 0);
+  return drt_attention_forward_bf16(qkv, mask, relbias, ctx, nullptr, nullptr, B, L, heads, head_dim, scale, 0.0f, 0, 0,
+                                    stream);
 }
 
 int drt_attention_relbias_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx,
                                               float* lse, uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads,
                                               int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                               uint64_t site, void* stream) {
-  return attention_fwd(qkv, mask, true, relbias, ctx, lse, drop_bits, B, L, heads, head_dim, scale, drop_p, seed, site,
-                       stream);
+  DRT_REQUIRE(relbias || B == 0);
+  return drt_attention_forward_bf16(qkv, mask, relbias, ctx, lse, drop_bits, B, L, heads, head_dim, scale, drop_p, seed,
+                                    site, stream);
 }
 
 int drt_pool_bf16(const void* hidden, const int64_t* mask, int64_t B, int64_t L, int32_t H, int32_t mode,

@@ -800,7 +800,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
 // Every score product, exponential and MFMA operand layout is the phase's of
 // attention_bwd_rk_kernel (same arithmetic per element).  The next block's global loads are issued
 // before the current block's matrix work (one barrier pair per block).  Dropout needs the forward's
-// keep bits (drt_attention_train_fwd_bits_bf16).  dsum: column sums per (sequence, 128-row group)
+// keep bits (drt_attention_forward_bf16's drop_bits).  dsum: column sums per (sequence, 128-row group)
 // [B][G][3H], reduced in a fixed order by the caller (deterministic).
 // ---------------------------------------------------------------------------
 constexpr int kAblMaxSeq = 512;
@@ -1238,27 +1238,117 @@ static int64_t attention_bwd_rows(int64_t B, int64_t L) {
   return L > kAbMaxSeq ? B * ((L + kAblGroup - 1) / kAblGroup) : B;
 }
 
-// The host driver behind the attention backward entries below (drt_attention_bwd_bf16, _train_bwd_bits,
-// _train_bwd_bias, _relbias_train_bwd): dqkv [B*L][3H] (dQ | dK | dV, head-major like qkv) of the
-// attention forward, given dctx = dO, the forward's ctx = O, lse and (drop_p, seed, site).
-// drop_bits: the forward's keep bits, read instead of re-hashing every (query, key) twice (dK / dV
-// and dQ phases); NULL = regenerate from the hash (L <= 160 only).  relbias: the forward's
-// relative-position bias, joins the score rebuild and comes with its gradient dtable [heads][2L-1]
-// -- the work-groups' diagonal sums of the fp32 dS (in ws), summed over the sequences in a fixed
-// order.  dbias [3H] = the column sums of dQKV (the query / key / value bias gradients) from partials
-// the kernels leave in ws, reduced in a fixed order -- no pass over dQKV.  No entry passes both
-// dbias and dtable: they share ws.
-static int attention_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int64_t* mask,
-                         const float* relbias, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
-                         int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
-                         float* dbias, float* dtable, void* ws, size_t ws_bytes, void* stream) {
+}  // namespace drt
+
+using namespace drt;
+
+extern "C" {
+
+size_t drt_colsum_workspace(int64_t M, int64_t N) {
+  if (M <= 0 || N <= 0) return 0;
+  const int64_t slabs = colsum_slabs(M, N);
+  return slabs > 1 ? (size_t)slabs * (size_t)N * sizeof(float) : 0;
+}
+
+int drt_colsum_f32(const float* x, int64_t M, int64_t N, float* out, void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(M >= 0 && N >= 0);
+  if (N == 0) return DRT_OK;
+  DRT_REQUIRE(out);
+  hipStream_t s = (hipStream_t)stream;
+  if (M == 0) return hip_status(hipMemsetAsync(out, 0, N * sizeof(float), s));
+  DRT_REQUIRE(x && ws_bytes >= drt_colsum_workspace(M, N) && (ws || drt_colsum_workspace(M, N) == 0));
+  return colsum_launch<float>(x, M, N, out, (float*)ws, s);
+}
+
+int drt_colsum_bf16(const void* x, int64_t M, int64_t N, float* out, void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(M >= 0 && N >= 0);
+  if (N == 0) return DRT_OK;
+  DRT_REQUIRE(out);
+  hipStream_t s = (hipStream_t)stream;
+  if (M == 0) return hip_status(hipMemsetAsync(out, 0, N * sizeof(float), s));
+  DRT_REQUIRE(x && ws_bytes >= drt_colsum_workspace(M, N) && (ws || drt_colsum_workspace(M, N) == 0));
+  return colsum_launch<__bf16>((const __bf16*)x, M, N, out, (float*)ws, s);
+}
+
+size_t drt_layernorm_bwd_workspace(int64_t M, int32_t H) {
+  if (M <= 0 || H <= 0) return 0;
+  return (size_t)3 * kLnBwdBlocks * (size_t)H * sizeof(float) + drt_colsum_workspace(kLnBwdBlocks, 2 * H);
+}
+
+// The LayerNorm backward with its optional dx_drop and dsum outputs (contract: drt.h).
+int drt_layernorm_backward_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
+                                const void* dres, void* dx, void* dx_drop, float drop_p, uint64_t seed, uint64_t site,
+                                float* dgamma, float* dbeta, float* dsum, void* ws, size_t ws_bytes, void* stream) {
+  DRT_REQUIRE(M > 0 && H > 0 && H % 256 == 0 && H <= 1024);
+  DRT_REQUIRE(!dx_drop || (drop_p >= 0.f && drop_p < 1.f));
+  DRT_REQUIRE(dy && x && gamma && dx && dgamma && dbeta && ws && ws_bytes >= drt_layernorm_bwd_workspace(M, H));
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)ws;   // [3 * blocks][H]: dgamma rows, dbeta rows, dsum rows
+  auto launch = [&](auto E, auto SUM) {
+    hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(E)::value, decltype(SUM)::value>), dim3(kLnBwdBlocks), dim3(256),
+                       0, s, (const __bf16*)dy, (const __bf16*)x, gamma, eps, M, (int)H, (const __bf16*)dres,
+                       (__bf16*)dx, part, (__bf16*)dx_drop, drop_p, seed, site);
+  };
+  int rc = dispatch_epl(H, [&](auto E) {
+    if (dsum) launch(E, std::true_type{});
+    else launch(E, std::false_type{});
+  });
+  if (rc) return rc;
+  float* ws2 = part + (size_t)3 * kLnBwdBlocks * H;
+  rc = colsum_launch<float>(part, kLnBwdBlocks, H, dgamma, ws2, s);
+  if (rc) return rc;
+  rc = colsum_launch<float>(part + (size_t)kLnBwdBlocks * H, kLnBwdBlocks, H, dbeta, ws2, s);
+  if (rc || !dsum) return rc;
+  return colsum_launch<float>(part + (size_t)2 * kLnBwdBlocks * H, kLnBwdBlocks, H, dsum, ws2, s);
+}
+
+// The earlier name: without dx_drop and dsum.
+int drt_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
+                           const void* dres, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                           void* stream) {
+  return drt_layernorm_backward_bf16(dy, x, gamma, eps, M, H, dres, dx, nullptr, 0.f, 0, 0, dgamma, dbeta, nullptr, ws,
+                                     ws_bytes, stream);
+}
+
+int drt_gelu_bwd_bf16(const void* dy, const void* pre, int64_t n, void* dx, void* stream) {
+  DRT_REQUIRE(n >= 0);
+  if (n == 0) return DRT_OK;
+  DRT_REQUIRE(dy && pre && dx);
+  const int64_t blocks = (n + 2047) / 2048;
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy,
+                     (const __bf16*)pre, n, (__bf16*)dx);
+  return hip_status(hipGetLastError());
+}
+
+// Bytes of ws behind the attention backward's optional output, then the column sum's own scratch.
+// dbias (rb = false): per-(sequence, 128-row group) partials [B][G <= 4][3H], sized for any
+// L <= 512 whatever L is.  dtable (rb = true): one row [heads][2L-1] per work-group
+// (attention_bwd_rows).
+static size_t attention_bwd_workspace(int64_t B, int64_t L, int32_t heads, int32_t head_dim, bool rb) {
+  if (B <= 0 || heads <= 0 || (rb ? L <= 0 || L > kAblMaxSeq : head_dim <= 0)) return 0;
+  const int64_t n = rb ? (int64_t)heads * (2 * L - 1) : 3 * (int64_t)heads * head_dim;
+  const int64_t rows = rb ? attention_bwd_rows(B, L) : B * (kAblMaxSeq / kAblGroup);
+  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
+}
+
+size_t drt_attention_backward_workspace(int64_t B, int64_t L, int32_t heads, int32_t head_dim, int32_t with_relbias) {
+  return attention_bwd_workspace(B, L, heads, head_dim, with_relbias != 0);
+}
+
+// The attention backward (contract: drt.h): every instantiation of the three backward kernels.
+// The kernels leave the partial sums of dbias or dtable in ws (one row per attention_bwd_rows), a
+// fixed-order column sum finishes them; the two share ws, so both together are refused.
+int drt_attention_backward_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                const int64_t* mask, const float* relbias, const uint32_t* drop_bits, void* dqkv,
+                                int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale, float drop_p,
+                                uint64_t seed, uint64_t site, float* dbias, float* dtable, void* ws, size_t ws_bytes,
+                                void* stream) {
   DRT_REQUIRE(B >= 0 && L > 0 && L <= kAblMaxSeq && heads > 0 && head_dim == 64);
-  DRT_REQUIRE(!relbias == !dtable);
+  DRT_REQUIRE(!relbias == !dtable && !(dbias && dtable));
   DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
   float* part = dbias || dtable ? (float*)ws : nullptr;   // the kernels' partial sums
   if (dbias || dtable)
-    DRT_REQUIRE(B > 0 && ws && ws_bytes >= (dbias ? drt_attention_train_bwd_bias_workspace(B, heads, head_dim)
-                                                   : drt_attention_relbias_train_bwd_workspace(B, L, heads)));
+    DRT_REQUIRE(B > 0 && ws && ws_bytes >= attention_bwd_workspace(B, L, heads, head_dim, dtable != nullptr));
   if (B == 0) return DRT_OK;
   DRT_REQUIRE(qkv && ctx && dctx && lse && dqkv);
   AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, mask, (__bf16*)dqkv, B, L,
@@ -1313,119 +1403,28 @@ static int attention_bwd(const void* qkv, const void* ctx, const void* dctx, con
   return colsum_launch<float>(part, rows, n, dtable, part + (size_t)rows * n, st);
 }
 
-}  // namespace drt
-
-using namespace drt;
-
-extern "C" {
-
-size_t drt_colsum_workspace(int64_t M, int64_t N) {
-  if (M <= 0 || N <= 0) return 0;
-  const int64_t slabs = colsum_slabs(M, N);
-  return slabs > 1 ? (size_t)slabs * (size_t)N * sizeof(float) : 0;
-}
-
-int drt_colsum_f32(const float* x, int64_t M, int64_t N, float* out, void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(M >= 0 && N >= 0);
-  if (N == 0) return DRT_OK;
-  DRT_REQUIRE(out);
-  hipStream_t s = (hipStream_t)stream;
-  if (M == 0) return hip_status(hipMemsetAsync(out, 0, N * sizeof(float), s));
-  DRT_REQUIRE(x && ws_bytes >= drt_colsum_workspace(M, N) && (ws || drt_colsum_workspace(M, N) == 0));
-  return colsum_launch<float>(x, M, N, out, (float*)ws, s);
-}
-
-int drt_colsum_bf16(const void* x, int64_t M, int64_t N, float* out, void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(M >= 0 && N >= 0);
-  if (N == 0) return DRT_OK;
-  DRT_REQUIRE(out);
-  hipStream_t s = (hipStream_t)stream;
-  if (M == 0) return hip_status(hipMemsetAsync(out, 0, N * sizeof(float), s));
-  DRT_REQUIRE(x && ws_bytes >= drt_colsum_workspace(M, N) && (ws || drt_colsum_workspace(M, N) == 0));
-  return colsum_launch<__bf16>((const __bf16*)x, M, N, out, (float*)ws, s);
-}
-
-size_t drt_layernorm_bwd_workspace(int64_t M, int32_t H) {
-  if (M <= 0 || H <= 0) return 0;
-  return (size_t)3 * kLnBwdBlocks * (size_t)H * sizeof(float) + drt_colsum_workspace(kLnBwdBlocks, 2 * H);
-}
-
-// dx = LN backward of dy through out = LN(x) (gamma; x = the bf16 pre-LN sums the forward
-// stored) + dres (residual gradient, may be NULL); dgamma / dbeta fp32 [H] (deterministic).
-// dx_drop (optional) = dropout(dx) with drt_dropout_add_bf16's mask of (drop_p, seed, site): the
-// gradient entering the linear whose output HF dropped before this LayerNorm's residual add.
-// dsum (optional) [H] fp32 = the column sums of the gradient handed down (dx_drop, or dx without
-// dropout) -- the bias gradient of the linear feeding this LayerNorm.
-int drt_layernorm_bwd_sum_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
-                               const void* dres, void* dx, void* dx_drop, float drop_p, uint64_t seed, uint64_t site,
-                               float* dgamma, float* dbeta, float* dsum, void* ws, size_t ws_bytes, void* stream) {
-  DRT_REQUIRE(M > 0 && H > 0 && H % 256 == 0 && H <= 1024);
-  DRT_REQUIRE(!dx_drop || (drop_p >= 0.f && drop_p < 1.f));
-  DRT_REQUIRE(dy && x && gamma && dx && dgamma && dbeta && ws && ws_bytes >= drt_layernorm_bwd_workspace(M, H));
-  hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;   // [3 * blocks][H]: dgamma rows, dbeta rows, dsum rows
-  auto launch = [&](auto E, auto SUM) {
-    hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(E)::value, decltype(SUM)::value>), dim3(kLnBwdBlocks), dim3(256),
-                       0, s, (const __bf16*)dy, (const __bf16*)x, gamma, eps, M, (int)H, (const __bf16*)dres,
-                       (__bf16*)dx, part, (__bf16*)dx_drop, drop_p, seed, site);
-  };
-  int rc = dispatch_epl(H, [&](auto E) {
-    if (dsum) launch(E, std::true_type{});
-    else launch(E, std::false_type{});
-  });
-  if (rc) return rc;
-  float* ws2 = part + (size_t)3 * kLnBwdBlocks * H;
-  rc = colsum_launch<float>(part, kLnBwdBlocks, H, dgamma, ws2, s);
-  if (rc) return rc;
-  rc = colsum_launch<float>(part + (size_t)kLnBwdBlocks * H, kLnBwdBlocks, H, dbeta, ws2, s);
-  if (rc || !dsum) return rc;
-  return colsum_launch<float>(part + (size_t)2 * kLnBwdBlocks * H, kLnBwdBlocks, H, dsum, ws2, s);
-}
-
-int drt_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M, int32_t H,
-                           const void* dres, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
-                           void* stream) {
-  return drt_layernorm_bwd_sum_bf16(dy, x, gamma, eps, M, H, dres, dx, nullptr, 0.f, 0, 0, dgamma, dbeta, nullptr, ws,
-                                    ws_bytes, stream);
-}
-
-int drt_gelu_bwd_bf16(const void* dy, const void* pre, int64_t n, void* dx, void* stream) {
-  DRT_REQUIRE(n >= 0);
-  if (n == 0) return DRT_OK;
-  DRT_REQUIRE(dy && pre && dx);
-  const int64_t blocks = (n + 2047) / 2048;
-  hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dy,
-                     (const __bf16*)pre, n, (__bf16*)dx);
-  return hip_status(hipGetLastError());
-}
-
-// Sized for any L <= 512: per-(sequence, 128-row group) partials [B][G <= 4][3H] + the colsum's own.
+// The earlier names (drt.h, "Earlier attention names"): argument subsets of the two entries above.
 size_t drt_attention_train_bwd_bias_workspace(int64_t B, int32_t heads, int32_t head_dim) {
-  if (B <= 0 || heads <= 0 || head_dim <= 0) return 0;
-  const int64_t n = 3 * (int64_t)heads * head_dim, rows = B * (kAblMaxSeq / kAblGroup);
-  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
+  return attention_bwd_workspace(B, 0, heads, head_dim, false);
 }
 
-// One row [heads][2L-1] per work-group (attention_bwd_rows), then the column sum's own scratch.
 size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads) {
-  if (B <= 0 || L <= 0 || L > kAblMaxSeq || heads <= 0) return 0;
-  const int64_t n = (int64_t)heads * (2 * L - 1), rows = attention_bwd_rows(B, L);
-  return (size_t)rows * n * sizeof(float) + drt_colsum_workspace(rows, n);
+  return attention_bwd_workspace(B, L, heads, 64, true);
 }
 
 int drt_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                            const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
                            float scale, void* stream) {
-  return attention_bwd(qkv, ctx, dctx, lse, mask, nullptr, nullptr, dqkv, B, L, heads, head_dim, scale, 0.0f, 0, 0,
-                       nullptr, nullptr, nullptr, 0, stream);
+  return drt_attention_backward_bf16(qkv, ctx, dctx, lse, mask, nullptr, nullptr, dqkv, B, L, heads, head_dim, scale,
+                                     0.0f, 0, 0, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int drt_attention_train_bwd_bits_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                                       const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
                                       int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                       uint64_t site, void* stream) {
-  return attention_bwd(qkv, ctx, dctx, lse, mask, nullptr, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
-                       site, nullptr, nullptr, nullptr, 0, stream);
+  return drt_attention_backward_bf16(qkv, ctx, dctx, lse, mask, nullptr, drop_bits, dqkv, B, L, heads, head_dim, scale,
+                                     drop_p, seed, site, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
@@ -1433,8 +1432,8 @@ int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const vo
                                       int32_t heads, int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                       uint64_t site, float* dbias, void* ws, size_t ws_bytes, void* stream) {
   DRT_REQUIRE(dbias);
-  return attention_bwd(qkv, ctx, dctx, lse, mask, nullptr, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
-                       site, dbias, nullptr, ws, ws_bytes, stream);
+  return drt_attention_backward_bf16(qkv, ctx, dctx, lse, mask, nullptr, drop_bits, dqkv, B, L, heads, head_dim, scale,
+                                     drop_p, seed, site, dbias, nullptr, ws, ws_bytes, stream);
 }
 
 int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
@@ -1443,8 +1442,8 @@ int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const
                                          float scale, float drop_p, uint64_t seed, uint64_t site, float* dtable,
                                          void* ws, size_t ws_bytes, void* stream) {
   DRT_REQUIRE(relbias && dtable);
-  return attention_bwd(qkv, ctx, dctx, lse, mask, relbias, drop_bits, dqkv, B, L, heads, head_dim, scale, drop_p, seed,
-                       site, nullptr, dtable, ws, ws_bytes, stream);
+  return drt_attention_backward_bf16(qkv, ctx, dctx, lse, mask, relbias, drop_bits, dqkv, B, L, heads, head_dim, scale,
+                                     drop_p, seed, site, nullptr, dtable, ws, ws_bytes, stream);
 }
 
 int drt_dropout_add_bf16(const void* y, const void* resid, int64_t n, float p, uint64_t seed, uint64_t site,

@@ -1,7 +1,7 @@
 // T5 encoder forward kernels (HF T5EncoderModel in eval mode: transformers/models/t5/modeling_t5.py
 // T5Stack embedding, T5LayerNorm, T5DenseGatedActDense).  The projections are the bf16 GEMMs of
 // gemm.hip (ReLU: epilogue flag bit 3) and the attention is the RB instantiation of encoder.hip's
-// kernel (drt_attention_relbias_bf16).
+// kernel (drt_attention_forward_bf16 with relbias).
 //
 //   t5_embed     shared.weight[ids] -> the bf16 residual stream (no position / type table, no norm)
 //   rmsnorm      x * rsqrt(mean(x^2) + eps) * w, fp32 statistics, no mean, no bias

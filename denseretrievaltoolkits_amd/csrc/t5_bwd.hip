@@ -2,7 +2,7 @@
 // T5LayerNorm, T5DenseActDense / T5DenseGatedActDense, the shared embedding) for the bf16
 // activations the training forward stores (model/t5_train_tower.py).  The projections' gradients
 // are the GEMMs of gemm.hip, the attention backward with the relative-position bias is the RB
-// instantiation of encoder_bwd.hip's kernels (drt_attention_relbias_train_bwd_bf16).
+// instantiation of encoder_bwd.hip's kernels (drt_attention_backward_bf16 with relbias).
 //
 //   rmsnorm_bwd         y = x r g, r = rsqrt(mean x^2 + eps):
 //                       dx = g dy r - x r^3 mean(g dy x) (+ a residual gradient),

@@ -787,9 +787,10 @@ Tensor attention(const Tensor& qkv_, const c10::optional<Tensor>& mask, int64_t 
     m = mask->to(at::kLong).contiguous();
   }
   Tensor ctx = at::empty({T, heads * hd}, qkv.options());
-  check_rc(drt_attention_bf16(qkv.data_ptr(), m.has_value() ? m->data_ptr<int64_t>() : nullptr, ctx.data_ptr(), B, L,
-                              (int32_t)heads, (int32_t)hd, (float)scale, stream_of(qkv)),
-           "drt_attention_bf16");
+  check_rc(drt_attention_forward_bf16(qkv.data_ptr(), m.has_value() ? m->data_ptr<int64_t>() : nullptr, nullptr,
+                                      ctx.data_ptr(), nullptr, nullptr, B, L, (int32_t)heads, (int32_t)hd,
+                                      (float)scale, 0.0f, 0, 0, stream_of(qkv)),
+           "drt_attention_forward_bf16");
   return ctx;
 }
 

@@ -265,11 +265,12 @@ class HipBertEncoder:
         nb = self._ws_bytes(T)
         self._ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev) if nb else None
         scale = 1.0 / math.sqrt(H // sh.heads)
+        mp = mask.data_ptr() if mask is not None else None
         for ly in self.layers:
             self._lin(h, ly["wqkv"], ly["bqkv"], qkv)
-            _native.check(self.lib.drt_attention_bf16(qkv.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                                      ctx.data_ptr(), B, L, sh.heads, H // sh.heads, scale,
-                                                      self.stream), "drt_attention_bf16")
+            _native.check(self.lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, None, ctx.data_ptr(), None, None, B, L,
+                                                              sh.heads, H // sh.heads, scale, 0.0, 0, 0, self.stream),
+                          "drt_attention_forward_bf16")
             self._lin_ln(ctx, ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], x32, ln)
             self._lin(h, ly["wi"], ly["bi"], ffn, gelu=True)
             self._lin_ln(ffn, ly["wf"], ly["bf"], h, ly["g2"], ly["b2"], x32, ln)

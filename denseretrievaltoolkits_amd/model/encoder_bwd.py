@@ -88,15 +88,9 @@ def attention_forward(qkv, mask, B, L, heads, scale, relbias=None, drop=None):
     lse = torch.empty((B, heads, L), dtype=torch.float32, device=dev)
     p, seed, site = drop if drop is not None else (0.0, 0, 0)
     bits = torch.empty((B, heads, L, (L + 31) // 32), dtype=torch.int32, device=dev) if p > 0 else None
-    lib = _native.load()
-    tail = (ctx.data_ptr(), lse.data_ptr(), _ptr(bits), B, L, heads, 64, float(scale), float(p), seed, site,
-            _native.stream_ptr(dev))
-    if relbias is None:
-        _native.check(lib.drt_attention_train_fwd_bits_bf16(qkv.data_ptr(), _ptr(mask), *tail),
-                      "drt_attention_train_fwd_bits_bf16")
-    else:
-        _native.check(lib.drt_attention_relbias_train_fwd_bits_bf16(qkv.data_ptr(), _ptr(mask), relbias.data_ptr(),
-                                                                    *tail), "drt_attention_relbias_train_fwd_bits_bf16")
+    _native.check(_native.load().drt_attention_forward_bf16(
+        qkv.data_ptr(), _ptr(mask), _ptr(relbias), ctx.data_ptr(), lse.data_ptr(), _ptr(bits), B, L, heads, 64,
+        float(scale), float(p), seed, site, _native.stream_ptr(dev)), "drt_attention_forward_bf16")
     return ctx, lse, bits
 
 
@@ -109,24 +103,16 @@ def attention_backward(qkv, ctx, dctx, lse, mask, bits, B, L, heads, scale, relb
     dev = qkv.device
     dqkv = torch.empty_like(qkv)
     p, seed, site = drop if drop is not None else (0.0, 0, 0)
-    head = (qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), _ptr(mask))
-    tail = (_ptr(bits), dqkv.data_ptr(), B, L, heads, 64, float(scale), float(p), seed, site)
-    s = _native.stream_ptr(dev)
-    if relbias is not None:
-        extra = torch.empty((heads, 2 * L - 1), dtype=torch.float32, device=dev)
-        nb = int(lib.drt_attention_relbias_train_bwd_workspace(B, L, heads))
-        ws = _ws(nb, dev)
-        _native.check(lib.drt_attention_relbias_train_bwd_bf16(*head, relbias.data_ptr(), *tail, extra.data_ptr(),
-                                                               _ptr(ws), nb, s), "drt_attention_relbias_train_bwd_bf16")
-    elif want_dbias:
-        extra = torch.empty(3 * heads * 64, dtype=torch.float32, device=dev)
-        nb = int(lib.drt_attention_train_bwd_bias_workspace(B, heads, 64))
-        ws = _ws(nb, dev)
-        _native.check(lib.drt_attention_train_bwd_bias_bf16(*head, *tail, extra.data_ptr(), _ptr(ws), nb, s),
-                      "drt_attention_train_bwd_bias_bf16")
-    else:
-        extra = None
-        _native.check(lib.drt_attention_train_bwd_bits_bf16(*head, *tail, s), "drt_attention_train_bwd_bits_bf16")
+    rb = relbias is not None
+    shape = (heads, 2 * L - 1) if rb else (3 * heads * 64,) if want_dbias else None
+    extra = torch.empty(shape, dtype=torch.float32, device=dev) if shape else None
+    nb = int(lib.drt_attention_backward_workspace(B, L, heads, 64, int(rb))) if shape else 0
+    ws = _ws(nb, dev)
+    dbias, dtable = (None, extra) if rb else (extra, None)
+    _native.check(lib.drt_attention_backward_bf16(
+        qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), _ptr(mask), _ptr(relbias), _ptr(bits),
+        dqkv.data_ptr(), B, L, heads, 64, float(scale), float(p), seed, site, _ptr(dbias), _ptr(dtable), _ptr(ws), nb,
+        _native.stream_ptr(dev)), "drt_attention_backward_bf16")
     return dqkv, extra
 
 
@@ -241,10 +227,10 @@ def layernorm_backward(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, e
     dxd = torch.empty_like(dx) if drop is not None else None
     p, seed, site = drop if drop is not None else (0.0, 0, 0)
     dsum = torch.empty(H, dtype=torch.float32, device=dev) if want_sum else None
-    _native.check(lib.drt_layernorm_bwd_sum_bf16(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), float(eps), M, H,
-                                                 _ptr(dres), dx.data_ptr(), _ptr(dxd), float(p), seed, site,
-                                                 dg.data_ptr(), db.data_ptr(), _ptr(dsum), _ptr(ws), nb,
-                                                 _native.stream_ptr(dev)), "drt_layernorm_bwd_sum_bf16")
+    _native.check(lib.drt_layernorm_backward_bf16(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), float(eps), M, H,
+                                                  _ptr(dres), dx.data_ptr(), _ptr(dxd), float(p), seed, site,
+                                                  dg.data_ptr(), db.data_ptr(), _ptr(dsum), _ptr(ws), nb,
+                                                  _native.stream_ptr(dev)), "drt_layernorm_backward_bf16")
     out = (dx, dg, db) + ((dxd,) if drop is not None else ()) + ((dsum,) if want_sum else ())
     return out
 

@@ -243,9 +243,9 @@ class HipT5Encoder:
         for ly in self.layers:
             self._rms(h, ly["g0"], x)
             self._lin(x, ly["wqkv"], qkv)
-            _native.check(lib.drt_attention_relbias_bf16(qkv.data_ptr(), mp, table.data_ptr(), ctx.data_ptr(), B, L,
-                                                         sh.heads, sh.d_kv, 1.0, self.stream),
-                          "drt_attention_relbias_bf16")
+            _native.check(lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, table.data_ptr(), ctx.data_ptr(), None, None,
+                                                         B, L, sh.heads, sh.d_kv, 1.0, 0.0, 0, 0, self.stream),
+                          "drt_attention_forward_bf16")
             self._lin(ctx, ly["wo"], h2, resid=h)
             self._rms(h2, ly["g1"], x)
             if gated:

@@ -352,9 +352,7 @@ int drt_gemm_nt_bf16_f32(const void* A, const void* B, float* C, int64_t m, int6
  * drt_layernorm_f32_bf16: out bf16 = LN(X fp32 [M,H]).
  * drt_layernorm_bf16: out bf16 = LN(X bf16 [M,H]) (fp32 statistics); the
  *   encoder's default, fed by a bf16 +bias +residual epilogue (one rounding).
- * drt_attention_bf16: ctx[B*L, heads*64] = softmax(Q K^T * scale + mask) V per
- *   head, from packed qkv [B*L, 3*heads*64]; mask int64 [B,L] (1 token, 0 pad)
- *   or NULL; L <= 512, head_dim == 64.
+ * drt_attention_forward_bf16: the self-attention of a layer; "Attention" below.
  * drt_pool_bf16: reps fp32 [B,H] (+ optional bf16 copy) from hidden bf16
  *   [B,L,H]; mode 0 first, 1 masked mean, 2 max(hidden*mask) (utils.py:233-240).
  * drt_l2_normalize_f32: in place x /= max(||x||_2, 1e-12) per row.          */
@@ -406,41 +404,134 @@ int drt_layernorm_f32_bf16(const float* X, int64_t M, int32_t H, const float* ga
                            const float* beta, float eps, void* out, void* stream);
 int drt_layernorm_bf16(const void* X, int64_t M, int32_t H, const float* gamma,
                        const float* beta, float eps, void* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Attention: one forward and one backward for BERT and T5 layers, inference and training
+ * (BertSelfAttention, modeling_bert.py:164-204; T5Attention, modeling_t5.py).  head_dim == 64,
+ * 0 < L <= 512, 0 <= drop_p < 1; a bad shape or argument is DRT_EINVAL before any HIP call, B == 0
+ * is DRT_OK after the shape checks.  H = heads * 64.
+ * ------------------------------------------------------------------------
+ * drt_attention_forward_bf16: ctx [B*L, H] bf16 = softmax(Q K^T * scale + relbias + mask) V per
+ *   head, from packed qkv [B*L, 3H] bf16 (Q | K | V, head-major).
+ *   mask int64 [B, L] (1 token, 0 pad) or NULL.  A masked key keeps finfo.min (a relbias is
+ *     absorbed), so a sequence with every key masked gets the uniform softmax over its L keys.
+ *   relbias fp32 [heads][2L-1] or NULL: entry (h, k - q + L - 1) is added to the score of query q
+ *     and key k before the softmax (T5's relative-position bias; T5 passes scale = 1).  An all-zero
+ *     table gives the bits of relbias = NULL, in ctx and in the backward's dqkv.
+ *   lse (optional output, NULL = without) fp32 [B][heads][L] = the log-sum-exp of each query's
+ *     scaled, biased, masked scores: the input of the backward.  ctx has the same bits with and
+ *     without it.
+ *   drop_p > 0: dropout of the probabilities (HF train mode).  The keep of (b, head, q, key) is
+ *     drawn from the pairwise hash of csrc/drt_common.h (attn_row_key / attn_keep) for (drop_p,
+ *     seed, site); drop_p = 0 is the plain forward / backward, with the inference bits in ctx.
+ *   drop_bits (optional output) u32 [B][heads][L][ceil(L / 32)]: the keep mask as bits, bit
+ *     key & 31 of word (query, key >> 5); written only when drop_p > 0 and drop_bits != NULL.
+ * drt_attention_backward_bf16: dqkv [B*L, 3H] bf16 (dQ | dK | dV in qkv's packed layout) from qkv,
+ *   the forward's ctx = O and lse, dctx = dO, and the forward's mask, relbias, scale and (drop_p,
+ *   seed, site).  The scores are rebuilt as S = Qs K^T + relbias[h][k - q + L - 1] + key bias.
+ *   L <= 160: one work-group per (sequence, head) holding the sequence in LDS; 160 < L <= 512:
+ *     streamed dK / dV and dQ kernels over 128-row groups.
+ *   drop_bits: the forward's keep bits, read instead of regenerating the hash twice per (query,
+ *     key); NULL = regenerate (same masks, same results).  For L > 160 with drop_p > 0 the
+ *     backward requires drop_bits (DRT_EINVAL without).
+ *   dbias (optional output) fp32 [3H] = the column sums of dQKV (the query / key / value bias
+ *     gradients of BertSelfAttention) from per-sequence (L > 160: per 128-row group) partials left
+ *     in ws, reduced in a fixed order, without a pass over dQKV.  dqkv has the same bits with and
+ *     without it.
+ *   dtable fp32 [heads][2L-1], the gradient of relbias: required with relbias, refused without.
+ *     dtable[h][d + L - 1] = sum over sequences and (q, k < L, k - q = d) of dS, taken from the fp32
+ *     dS before its bf16 rounding; padding rows and keys add nothing, a masked key adds an exact 0.
+ *     Each work-group sums its diagonals with LDS float atomics and leaves them in ws; the sum over
+ *     work-groups runs in a fixed order.  So dtable is reproducible up to the order of the LDS
+ *     atomics inside one (sequence, head); dqkv is bit-reproducible.
+ *   ws / ws_bytes: required with dbias or dtable (unused otherwise), at least
+ *     drt_attention_backward_workspace(B, L, heads, head_dim, with_relbias) bytes: with_relbias = 0
+ *     sizes dbias's partials (independent of L: sized for any L <= 512), with_relbias = 1 dtable's
+ *     (0 for L > 512).  dbias and dtable share ws, so both together are DRT_EINVAL.             */
+int drt_attention_forward_bf16(const void* qkv, const int64_t* mask, const float* relbias,
+                               void* ctx, float* lse, uint32_t* drop_bits,
+                               int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
+                               float drop_p, uint64_t seed, uint64_t site, void* stream);
+size_t drt_attention_backward_workspace(int64_t B, int64_t L, int32_t heads, int32_t head_dim,
+                                        int32_t with_relbias);
+int drt_attention_backward_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                const int64_t* mask, const float* relbias, const uint32_t* drop_bits,
+                                void* dqkv, int64_t B, int64_t L, int32_t heads, int32_t head_dim,
+                                float scale, float drop_p, uint64_t seed, uint64_t site,
+                                float* dbias, float* dtable, void* ws, size_t ws_bytes, void* stream);
+/* Earlier attention names, kept for callers that use them: each is the entry above with the
+ * arguments it does not list passed as NULL / 0 (nothing else: same checks, kernels and bits).
+ * drt_attention_bf16, _fwd_lse, _train_fwd_bits: the forward without relbias, and without lse /
+ *   dropout where not listed.  drt_attention_relbias_bf16, _relbias_train_fwd_bits: the same two
+ *   with relbias, which they require.  drt_attention_bwd_bf16, _train_bwd_bits: the backward without
+ *   relbias, dbias and ws; _train_bwd_bias: with dbias, which it requires; _relbias_train_bwd: with
+ *   relbias and dtable, which it requires.  The two queries are
+ *   drt_attention_backward_workspace(B, any L, heads, head_dim, 0) and (B, L, heads, 64, 1).   */
 int drt_attention_bf16(const void* qkv, const int64_t* mask, void* ctx, int64_t B, int64_t L,
                        int32_t heads, int32_t head_dim, float scale, void* stream);
-/* drt_attention_fwd_lse_bf16: the same forward, also writing lse [B][heads][L] fp32 = the
- * log-sum-exp of each query's scaled, masked scores (input of the attention backward).  */
 int drt_attention_fwd_lse_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse, int64_t B,
                                int64_t L, int32_t heads, int32_t head_dim, float scale, void* stream);
+int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse,
+                                      uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads,
+                                      int32_t head_dim, float scale, float drop_p, uint64_t seed,
+                                      uint64_t site, void* stream);
+int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx,
+                               int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
+                               void* stream);
+int drt_attention_relbias_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, const float* relbias,
+                                              void* ctx, float* lse, uint32_t* drop_bits, int64_t B,
+                                              int64_t L, int32_t heads, int32_t head_dim, float scale,
+                                              float drop_p, uint64_t seed, uint64_t site, void* stream);
+int drt_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                           const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads,
+                           int32_t head_dim, float scale, void* stream);
+int drt_attention_train_bwd_bits_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                      const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B,
+                                      int64_t L, int32_t heads, int32_t head_dim, float scale, float drop_p,
+                                      uint64_t seed, uint64_t site, void* stream);
+size_t drt_attention_train_bwd_bias_workspace(int64_t B, int32_t heads, int32_t head_dim);
+int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                      const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B,
+                                      int64_t L, int32_t heads, int32_t head_dim, float scale, float drop_p,
+                                      uint64_t seed, uint64_t site, float* dbias, void* ws, size_t ws_bytes,
+                                      void* stream);
+size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads);
+int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx,
+                                         const float* lse, const int64_t* mask, const float* relbias,
+                                         const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
+                                         int32_t heads, int32_t head_dim, float scale, float drop_p,
+                                         uint64_t seed, uint64_t site, float* dtable, void* ws,
+                                         size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Encoder backward building blocks (the gradient of HF BertModel's
  * ops as the training step of run_random_sampling.py takes it under autograd,
  * DRT/trainer/trainer.py:113-133; transformers modeling_bert.py:282-352).
  * ------------------------------------------------------------------------
- * drt_layernorm_bwd_bf16: dx [M,H] bf16 = LN backward of dy through LN(x) with gamma (x = the
+ * drt_layernorm_backward_bf16: dx [M,H] bf16 = LN backward of dy through LN(x) with gamma (x = the
  *   bf16 pre-LN sums the forward stored; statistics recomputed) + dres (residual gradient or
  *   NULL); dgamma / dbeta fp32 [H], deterministic (fixed-order partial sums in ws of
- *   drt_layernorm_bwd_workspace(M, H) bytes).  H % 256 == 0, H <= 1024.
+ *   drt_layernorm_bwd_workspace(M, H) bytes).  H % 256 == 0, H <= 1024.  Two optional outputs
+ *   (NULL = without): dx_drop = dropout(dx) with drt_dropout_add_bf16's mask of (drop_p, seed,
+ *   site) at the flat index m * H + h (the gradient of a linear whose output was dropped before
+ *   this LayerNorm's residual add; replaces a separate dropout pass), and dsum [H] fp32 = the
+ *   column sums of the gradient it hands down (dx_drop, or dx when dx_drop is NULL): the bias
+ *   gradient of the linear feeding this LayerNorm (BertSelfOutput / BertOutput dense.bias)
+ *   without a separate pass over that gradient.
  * drt_colsum_bf16: out[n] fp32 = sum_rows x[row][n] (bias gradients), fixed order, ws of
  *   drt_colsum_workspace(M, N) bytes (0 for M < 256).
  * drt_gelu_bwd_bf16: dx = dy * (Phi(x) + x phi(x)) for the erf GELU (pre = the FFN1
  *   pre-activation), n elements.
  * drt_transpose_bf16: y [C,R] = x [R,C]^T (operand layout for the weight gradients).      */
 size_t drt_layernorm_bwd_workspace(int64_t M, int32_t H);
+int drt_layernorm_backward_bf16(const void* dy, const void* x, const float* gamma, float eps,
+                                int64_t M, int32_t H, const void* dres, void* dx, void* dx_drop,
+                                float drop_p, uint64_t seed, uint64_t site, float* dgamma,
+                                float* dbeta, float* dsum, void* ws, size_t ws_bytes, void* stream);
+/* drt_layernorm_bwd_bf16: the earlier name of the call without dx_drop and dsum.   */
 int drt_layernorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M,
                            int32_t H, const void* dres, void* dx, float* dgamma, float* dbeta,
                            void* ws, size_t ws_bytes, void* stream);
-/* drt_layernorm_bwd_sum_bf16: the same with two optional outputs (NULL = without): dx_drop =
- * dropout(dx) with drt_dropout_add_bf16's mask of (drop_p, seed, site) at the flat index m * H + h
- * (the gradient of a linear whose output was dropped before this LayerNorm's residual add; replaces
- * a separate dropout pass), and dsum [H] fp32 = the column sums of the gradient it hands down
- * (dx_drop, or dx when dx_drop is NULL): the bias gradient of the linear feeding this LayerNorm
- * (BertSelfOutput / BertOutput dense.bias) without a separate pass over that gradient.   */
-int drt_layernorm_bwd_sum_bf16(const void* dy, const void* x, const float* gamma, float eps,
-                               int64_t M, int32_t H, const void* dres, void* dx, void* dx_drop,
-                               float drop_p, uint64_t seed, uint64_t site, float* dgamma,
-                               float* dbeta, float* dsum, void* ws, size_t ws_bytes, void* stream);
 size_t drt_colsum_workspace(int64_t M, int64_t N);
 int drt_colsum_bf16(const void* x, int64_t M, int64_t N, float* out, void* ws, size_t ws_bytes,
                     void* stream);
@@ -457,11 +548,6 @@ int drt_transpose_bf16_ld(const void* x, int64_t R, int64_t C, void* y, int64_t 
 size_t drt_linear_wgrad_workspace(int64_t T, int64_t N, int64_t K);
 int drt_linear_wgrad_bf16(const void* dY, const void* X, float* dW, int64_t T, int64_t N, int64_t K, void* ws,
                           size_t ws_bytes, void* stream);
-/* drt_attention_bwd_bf16: dqkv [B*L, 3H] (dQ | dK | dV in qkv's packed layout) of the
- * attention forward, from qkv, its ctx = O, dctx = dO, the forward's lse and the key mask;
- * L <= 512, head_dim 64 (BertSelfAttention under autograd, modeling_bert.py:164-204);
- * L <= 160: one work-group per (sequence, head) holding the sequence in LDS; 160 < L <= 512:
- * streamed dK/dV and dQ kernels over 128-row groups (dropout there needs the forward's bits). */
 /* drt_embed_ln_pre: drt_embed_ln that also writes the bf16 pre-LN sum (word + type + pos).
  * drt_gelu_bf16: y = GELU(x) elementwise (erf form).
  * drt_embedding_bwd: scatter-add of d [B*L, H] (gradient of the pre-LN embedding sum) into
@@ -478,41 +564,12 @@ int drt_gelu_bf16(const void* x, int64_t n, void* y, void* stream);
 int drt_embedding_bwd(const int64_t* ids, const int64_t* type_ids, int32_t ntypes, const void* d,
                       int64_t B, int64_t L, int32_t H, int64_t padding_idx, float* dword, float* dpos,
                       float* dtype, void* stream);
-int drt_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                           const int64_t* mask, void* dqkv, int64_t B, int64_t L, int32_t heads,
-                           int32_t head_dim, float scale, void* stream);
 /* Training dropout (HF train mode, modeling_bert.py:107,195,296,348): keep element i of a
  * site iff drop_hash24(seed, site, i) >= p 2^24 (csrc/drt_common.h), kept values / (1 - p).
  * drt_dropout_add_bf16: out = dropout(y) + resid (resid may be NULL) over n elements; the
  *   same call on a gradient with resid = NULL is the dropout backward.                      */
 int drt_dropout_add_bf16(const void* y, const void* resid, int64_t n, float p, uint64_t seed, uint64_t site,
                          void* out, void* stream);
-/* The training attention pair: drt_attention_fwd_lse_bf16 / drt_attention_bwd_bf16 with dropout of
- * the probabilities (drop_p, seed, site; the keep of (b, head, q, key) is drawn from the pairwise
- * hash of csrc/drt_common.h, attn_row_key / attn_keep; p = 0 is the plain forward / backward) and
- * the keep mask kept as bits: the forward writes drop_bits [B][heads][L][ceil(L / 32)] u32 (bit
- * key & 31 of word (query, key >> 5); only when drop_p > 0 and drop_bits != NULL), the backward
- * reads them instead of regenerating the hash twice per (query, key); NULL drop_bits = regenerate
- * (same masks, same results).  For L > 160 with drop_p > 0 the backward requires drop_bits
- * (DRT_EINVAL without).                                                                        */
-int drt_attention_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, void* ctx, float* lse,
-                                      uint32_t* drop_bits, int64_t B, int64_t L, int32_t heads,
-                                      int32_t head_dim, float scale, float drop_p, uint64_t seed,
-                                      uint64_t site, void* stream);
-int drt_attention_train_bwd_bits_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                      const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B,
-                                      int64_t L, int32_t heads, int32_t head_dim, float scale, float drop_p,
-                                      uint64_t seed, uint64_t site, void* stream);
-/* drt_attention_train_bwd_bias_bf16: the same, also writing dbias [3H] fp32 = the column sums of
- * dQKV (the query / key / value bias gradients of BertSelfAttention) from per-sequence (L > 160:
- * per 128-row group) partials left in ws (drt_attention_train_bwd_bias_workspace bytes, sized for
- * any L <= 512), reduced in a fixed order, without a pass over dQKV.                          */
-size_t drt_attention_train_bwd_bias_workspace(int64_t B, int32_t heads, int32_t head_dim);
-int drt_attention_train_bwd_bias_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                                      const int64_t* mask, const uint32_t* drop_bits, void* dqkv, int64_t B,
-                                      int64_t L, int32_t heads, int32_t head_dim, float scale, float drop_p,
-                                      uint64_t seed, uint64_t site, float* dbias, void* ws, size_t ws_bytes,
-                                      void* stream);
 int drt_pool_bf16(const void* hidden, const int64_t* mask, int64_t B, int64_t L, int32_t H,
                   int32_t mode, float* out, void* out_bf16, void* stream);
 int drt_l2_normalize_f32(float* x, int64_t B, int32_t H, void* out_bf16, void* stream);
@@ -526,11 +583,7 @@ int drt_l2_normalize_f32(float* x, int64_t B, int32_t H, void* out_bf16, void* s
  *   residual stream's first value, no position / type table and no norm.
  * drt_rmsnorm_bf16: out bf16 = X * rsqrt(mean(X^2) + eps) * weight over bf16 X [M, H] (T5LayerNorm:
  *   fp32 sum of squares, no mean, no bias, one rounding); H % 256 == 0, H <= 1024; out may alias X.
- * drt_attention_relbias_bf16: drt_attention_bf16 with relbias fp32 [heads][2L-1]: entry
- *   (h, k - q + L - 1) is added to the score of query q and key k before the softmax (T5 passes
- *   scale = 1).  A masked key keeps finfo.min (the bias is absorbed), so a sequence with every key
- *   masked gets the uniform softmax; an all-zero table gives drt_attention_bf16's bits.
- *   L <= 512, head_dim == 64; qkv [B*L, 3*heads*64], ctx [B*L, heads*64].
+ * drt_attention_forward_bf16 with relbias: the relative-position attention ("Attention" above).
  * drt_gated_gelu_new_bf16: out[M, F] bf16 = gelu_new(X[:, :F]) * X[:, F:] over bf16 X [M, 2F]
  *   (T5DenseGatedActDense after one GEMM over [wi_0; wi_1]); fp32 math, one rounding; F % 8 == 0,
  *   X and out 16-byte aligned.                                                                   */
@@ -538,25 +591,11 @@ int drt_t5_embed_bf16(const int64_t* ids, int64_t B, int64_t L, const float* tab
                       void* out, void* stream);
 int drt_rmsnorm_bf16(const void* X, int64_t M, int32_t H, const float* weight, float eps,
                      void* out, void* stream);
-int drt_attention_relbias_bf16(const void* qkv, const int64_t* mask, const float* relbias, void* ctx,
-                               int64_t B, int64_t L, int32_t heads, int32_t head_dim, float scale,
-                               void* stream);
 int drt_gated_gelu_new_bf16(const void* X, int64_t M, int64_t F, void* out, void* stream);
-/* T5 encoder training (HF T5EncoderModel under autograd): the attention forward / backward with the
- * relative-position bias, and the backwards of T5LayerNorm, the two feed-forward activations and
- * the shared embedding.  The projections use drt_linear_bf16* / drt_linear_wgrad_bf16.
- * drt_attention_relbias_train_fwd_bits_bf16: drt_attention_train_fwd_bits_bf16 (lse, attention-
- *   probability dropout, keep bits) with relbias as drt_attention_relbias_bf16 takes it; at
- *   drop_p = 0 ctx has drt_attention_relbias_bf16's bits.
- * drt_attention_relbias_train_bwd_bf16: drt_attention_train_bwd_bits_bf16 with that bias in the
- *   score rebuild (S = Qs K^T + relbias[h][k - q + L - 1] + key bias), also writing its gradient
- *   dtable fp32 [heads][2L-1]: dtable[h][d + L - 1] = sum over sequences and (q, k < L, k - q = d)
- *   of dS, taken from the fp32 dS before its bf16 rounding; padding rows and keys add nothing, a
- *   masked key adds an exact 0.  Each work-group sums its diagonals with LDS float atomics and
- *   leaves them in ws (drt_attention_relbias_train_bwd_workspace bytes); the sum over work-groups
- *   runs in a fixed order.  So dtable is reproducible up to the order of the LDS atomics inside one
- *   (sequence, head); dqkv is bit-reproducible, and with an all-zero relbias it has
- *   drt_attention_train_bwd_bits_bf16's bits.  L <= 512 (L > 160 with dropout needs drop_bits).
+/* T5 encoder training (HF T5EncoderModel under autograd): drt_attention_forward_bf16 /
+ * drt_attention_backward_bf16 with relbias and dtable ("Attention" above), and the backwards of
+ * T5LayerNorm, the two feed-forward activations and the shared embedding.  The projections use
+ * drt_linear_bf16* / drt_linear_wgrad_bf16.
  * drt_rmsnorm_bwd_bf16: for y = x r gamma, r = rsqrt(mean x^2 + eps) over bf16 x [M, H]:
  *   dx = gamma dy r - x r^3 mean(gamma dy x) (+ dres, a residual gradient, may be NULL), bf16;
  *   dgamma fp32 [H] = sum_rows dy x r from per-block partials summed in a fixed order
@@ -568,17 +607,6 @@ int drt_gated_gelu_new_bf16(const void* X, int64_t M, int64_t F, void* out, void
  *   index (HF drops f before wo); drop_p = 0: none.  Pointers 16-byte aligned.
  * drt_t5_embedding_bwd: dshared[ids[t]] += d[t] over bf16 d [B*L, H] into fp32 dshared [vocab, H]
  *   (the caller zeroes it; fp32 atomics; no position / type table, no padding row).           */
-int drt_attention_relbias_train_fwd_bits_bf16(const void* qkv, const int64_t* mask, const float* relbias,
-                                              void* ctx, float* lse, uint32_t* drop_bits, int64_t B,
-                                              int64_t L, int32_t heads, int32_t head_dim, float scale,
-                                              float drop_p, uint64_t seed, uint64_t site, void* stream);
-size_t drt_attention_relbias_train_bwd_workspace(int64_t B, int64_t L, int32_t heads);
-int drt_attention_relbias_train_bwd_bf16(const void* qkv, const void* ctx, const void* dctx,
-                                         const float* lse, const int64_t* mask, const float* relbias,
-                                         const uint32_t* drop_bits, void* dqkv, int64_t B, int64_t L,
-                                         int32_t heads, int32_t head_dim, float scale, float drop_p,
-                                         uint64_t seed, uint64_t site, float* dtable, void* ws,
-                                         size_t ws_bytes, void* stream);
 size_t drt_rmsnorm_bwd_workspace(int64_t M, int32_t H);
 int drt_rmsnorm_bwd_bf16(const void* dy, const void* x, const float* gamma, float eps, int64_t M,
                          int32_t H, const void* dres, void* dx, float* dgamma, void* ws,
@@ -598,7 +626,7 @@ int drt_t5_embedding_bwd(const int64_t* ids, const void* d, int64_t B, int64_t L
  * drt_t5_cross_pool_bf16: per (sequence, head) p = softmax_l(qt[b,h,:] . enc[b,l,:]) (no scale, no
  *   bias) and pooled[b, h, :] = sum_l p_l enc[b, l, :], bf16 [B, heads, D]; enc is read once, the
  *   softmax is online in fp32 (P rounded to bf16 for the MFMA, fp32 accumulators, one output
- *   rounding).  mask int64 [B, L] or NULL with drt_attention_relbias_bf16's convention: a masked
+ *   rounding).  mask int64 [B, L] or NULL with drt_attention_forward_bf16's convention: a masked
  *   key contributes nothing whatever finite value enc holds there, a sequence with every key masked
  *   gets the uniform softmax over its L keys.  1 <= L <= 512; qt and enc 16-byte aligned.
  * drt_t5_head_reduce_bf16: ctx[b, 64h+j] = Wv[64h+j, :] . pooled[b, h, :] -> bf16 ctx [B, heads*64];

@@ -4,6 +4,8 @@ transformers modeling_bert.py:164-204, 282-352) on the same bf16 inputs."""
 import numpy as np
 import pytest
 
+import attention_abi as abi
+
 pytestmark = pytest.mark.gpu
 
 
@@ -28,17 +30,19 @@ def test_layernorm_bwd_vs_torch(dev, M, H, resid):
     dx = torch.empty(M, H, dtype=torch.bfloat16, device=dev)
     dgam = torch.empty(H, device=dev)
     dbet = torch.empty(H, device=dev)
-    _native.check(lib.drt_layernorm_bwd_bf16(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), 1e-12, M, H,
-                                             dres.data_ptr() if resid else None, dx.data_ptr(), dgam.data_ptr(),
-                                             dbet.data_ptr(), ws.data_ptr(), nb, _native.stream_ptr(dev)), "ln bwd")
+    _native.check(lib.drt_layernorm_backward_bf16(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), 1e-12, M, H,
+                                                  dres.data_ptr() if resid else None, dx.data_ptr(), None, 0.0, 0, 0,
+                                                  dgam.data_ptr(), dbet.data_ptr(), None, ws.data_ptr(), nb,
+                                                  _native.stream_ptr(dev)), "ln bwd")
     torch.testing.assert_close(dx.float(), ref_dx, atol=3e-2, rtol=1e-2)
     torch.testing.assert_close(dgam, gf.grad, atol=1e-3 * max(1.0, M ** 0.5), rtol=1e-4)
     torch.testing.assert_close(dbet, bf.grad, atol=1e-3 * max(1.0, M ** 0.5), rtol=1e-4)
     # deterministic: a second run gives identical bits
     dgam2 = torch.empty(H, device=dev)
-    _native.check(lib.drt_layernorm_bwd_bf16(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), 1e-12, M, H,
-                                             dres.data_ptr() if resid else None, dx.data_ptr(), dgam2.data_ptr(),
-                                             dbet.data_ptr(), ws.data_ptr(), nb, _native.stream_ptr(dev)), "ln bwd")
+    _native.check(lib.drt_layernorm_backward_bf16(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), 1e-12, M, H,
+                                                  dres.data_ptr() if resid else None, dx.data_ptr(), None, 0.0, 0, 0,
+                                                  dgam2.data_ptr(), dbet.data_ptr(), None, ws.data_ptr(), nb,
+                                                  _native.stream_ptr(dev)), "ln bwd")
     assert torch.equal(dgam, dgam2)
 
 
@@ -85,7 +89,7 @@ def test_transpose_bf16(dev, R, C):
 
 @pytest.mark.parametrize("B,L", [(4, 128), (3, 50), (2, 512), (5, 32)])
 def test_attention_lse_vs_torch(dev, B, L):
-    """drt_attention_fwd_lse_bf16: ctx unchanged vs drt_attention_bf16, and the per-query
+    """drt_attention_forward_bf16 with lse: ctx unchanged vs the call without, and the per-query
     log-sum-exp of the scaled, key-masked scores against torch fp32 on the same bf16 q/k."""
     import torch
     from denseretrievaltoolkits_amd import _native
@@ -99,11 +103,9 @@ def test_attention_lse_vs_torch(dev, B, L):
     ctx0 = torch.empty(B * L, H, dtype=torch.bfloat16, device=dev)
     ctx1 = torch.empty_like(ctx0)
     lse = torch.empty(B, heads, L, device=dev)
-    s = _native.stream_ptr(dev)
     scale = 1.0 / dh ** 0.5
-    _native.check(lib.drt_attention_bf16(qkv.data_ptr(), mask.data_ptr(), ctx0.data_ptr(), B, L, heads, dh, scale, s), "a")
-    _native.check(lib.drt_attention_fwd_lse_bf16(qkv.data_ptr(), mask.data_ptr(), ctx1.data_ptr(), lse.data_ptr(), B, L,
-                                                 heads, dh, scale, s), "lse")
+    _native.check(abi.forward(lib, qkv, ctx0, B, L, heads, mask=mask, scale=scale), "a")
+    _native.check(abi.forward(lib, qkv, ctx1, B, L, heads, mask=mask, lse=lse, scale=scale), "lse")
     assert torch.equal(ctx0, ctx1)
     q = qkv[:, :H].float().view(B, L, heads, dh).transpose(1, 2)
     k = qkv[:, H:2 * H].float().view(B, L, heads, dh).transpose(1, 2)
@@ -139,7 +141,7 @@ def test_linear_backward_vs_torch(dev, T, N, K):
 @pytest.mark.parametrize("B,L", [(4, 128), (3, 50), (6, 32), (2, 100), (3, 156), (2, 160), (2, 129),
                                  (3, 161), (2, 256), (3, 300), (2, 512)])
 def test_attention_bwd_vs_torch(dev, B, L):
-    """drt_attention_bwd_bf16 (dQ | dK | dV) against torch fp32 autograd of the same attention
+    """drt_attention_backward_bf16 (dQ | dK | dV) against torch fp32 autograd of the same attention
     (scaled scores + HF key mask, softmax, P V) on the same bf16 qkv, with padded sequences;
     L > 160 runs the streamed dK/dV + dQ kernels (128-row groups, ragged last group at 161, 300)."""
     import torch
@@ -153,15 +155,12 @@ def test_attention_bwd_vs_torch(dev, B, L):
     lens[0] = L
     mask = (torch.arange(L, device=dev)[None, :] < lens[:, None]).to(torch.int64)
     dctx = torch.randn(B * L, H, generator=g, device=dev).to(torch.bfloat16)
-    s = _native.stream_ptr(dev)
     scale = 1.0 / dh ** 0.5
     ctx = torch.empty(B * L, H, dtype=torch.bfloat16, device=dev)
     lse = torch.empty(B, heads, L, device=dev)
-    _native.check(lib.drt_attention_fwd_lse_bf16(qkv.data_ptr(), mask.data_ptr(), ctx.data_ptr(), lse.data_ptr(), B, L,
-                                                 heads, dh, scale, s), "fwd")
+    _native.check(abi.forward(lib, qkv, ctx, B, L, heads, mask=mask, lse=lse, scale=scale), "fwd")
     dqkv = torch.zeros(B * L, 3 * H, dtype=torch.bfloat16, device=dev)
-    _native.check(lib.drt_attention_bwd_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(),
-                                             mask.data_ptr(), dqkv.data_ptr(), B, L, heads, dh, scale, s), "bwd")
+    _native.check(abi.backward(lib, qkv, ctx, dctx, lse, dqkv, B, L, heads, mask=mask, scale=scale), "bwd")
     x = qkv.float().requires_grad_(True)
     q = x[:, :H].view(B, L, heads, dh).transpose(1, 2)
     k = x[:, H:2 * H].view(B, L, heads, dh).transpose(1, 2)
@@ -176,16 +175,14 @@ def test_attention_bwd_vs_torch(dev, B, L):
         assert err <= 2e-2 * max(1.0, want.abs().max().item()), (name, err, want.abs().max().item())
         cos = torch.nn.functional.cosine_similarity(got.flatten(), want.flatten(), dim=0).item()
         assert cos > 0.999, (name, cos)
-    # drt_attention_train_bwd_bias_bf16: the same dQKV bit for bit plus its column sums (the q / k / v
+    # with dbias: the same dQKV bit for bit plus its column sums (the q / k / v
     # bias gradients) = fp64 sums of the stored bf16 dQKV, to fp32 summation
     dqkv2 = torch.zeros_like(dqkv)
     dbias = torch.empty(3 * H, device=dev)
-    nb = int(lib.drt_attention_train_bwd_bias_workspace(B, heads, dh))
+    nb = int(lib.drt_attention_backward_workspace(B, L, heads, dh, 0))
     ws = torch.empty((nb + 3) // 4, device=dev)
-    _native.check(lib.drt_attention_train_bwd_bias_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
-                                                        lse.data_ptr(), mask.data_ptr(), None, dqkv2.data_ptr(), B,
-                                                        L, heads, dh, scale, 0.0, 0, 0, dbias.data_ptr(),
-                                                        ws.data_ptr(), nb, s), "bwd+bias")
+    _native.check(abi.backward(lib, qkv, ctx, dctx, lse, dqkv2, B, L, heads, mask=mask, scale=scale, dbias=dbias, ws=ws,
+                               ws_bytes=nb), "bwd+bias")
     torch.cuda.synchronize()
     assert torch.equal(dqkv2, dqkv)
     ref_b = dqkv.double().sum(0)
@@ -360,7 +357,7 @@ def test_linear_ex_dropout_vs_dropout_add(dev, M, N, K, p):
 
 @pytest.mark.parametrize("M,H", [(131072, 768), (37, 256)])
 def test_layernorm_bwd_drop_output_equals_dropout_kernel(dev, M, H):
-    """drt_layernorm_bwd_drop_bf16: dx identical to drt_layernorm_bwd_bf16 and dx_drop bit-identical
+    """drt_layernorm_backward_bf16 with dx_drop: dx identical to the call without and dx_drop bit-identical
     to drt_dropout_add_bf16(dx) with the same (p, seed, site)."""
     import torch
     from denseretrievaltoolkits_amd import _native
@@ -378,7 +375,7 @@ def test_layernorm_bwd_drop_output_equals_dropout_kernel(dev, M, H):
     torch.cuda.synchronize()
     assert torch.equal(dx, dx0) and torch.equal(dg, dg0) and torch.equal(db, db0)
     assert torch.equal(dxd, ref)
-    # drt_layernorm_bwd_sum_bf16: the same outputs plus the column sums of what it hands down
+    # with dsum: the same outputs plus the column sums of what it hands down
     # (the linear-bias gradient) = fp64 column sums of the stored bf16 gradient, to fp32 summation
     dx_s, dg_s, db_s, dxd_s, sd = layernorm_backward(dy, x, gamma, 1e-12, drop=(0.1, 99, 5), want_sum=True)
     dx_n, _, _, sn = layernorm_backward(dy, x, gamma, 1e-12, want_sum=True)
@@ -391,7 +388,7 @@ def test_layernorm_bwd_drop_output_equals_dropout_kernel(dev, M, H):
 
 @pytest.mark.parametrize("L,B", [(128, 6), (156, 5), (37, 9), (32, 4), (200, 3), (512, 2)])
 def test_attention_dropout_bits_vs_hash_and_torch(dev, L, B):
-    """drt_attention_train_fwd_bits_bf16 writes the attention-dropout keep mask as bits (the forward's
+    """drt_attention_forward_bf16 writes the attention-dropout keep mask as bits when asked (the forward's
     outputs do not change, the bits are the hash's keep decisions); the backward that reads them and
     the one that draws the same bits again from the hash (C-ABI callers without bits) both
     match torch fp32 autograd of the same dropped attention (the mask from the host restatement of the
@@ -401,7 +398,6 @@ def test_attention_dropout_bits_vs_hash_and_torch(dev, L, B):
     from denseretrievaltoolkits_amd import _native
     from tests.test_train_tower_gpu import _attn_keep_py, _attn_keep_torch
     lib = _native.load()
-    s = _native.stream_ptr(dev)
     heads, dh, p, seed, site = 12, 64, 0.1, 77, 3
     H = heads * dh
     scale = 1.0 / dh ** 0.5
@@ -416,13 +412,11 @@ def test_attention_dropout_bits_vs_hash_and_torch(dev, L, B):
         ctx = torch.empty(B * L, H, dtype=torch.bfloat16, device=dev)
         lse = torch.empty(B * heads * L, dtype=torch.float32, device=dev)
         bits = torch.full((B, heads, L, nkb), -1, dtype=torch.int32, device=dev) if use_bits else None
-        _native.check(lib.drt_attention_train_fwd_bits_bf16(qkv.data_ptr(), mask.data_ptr(), ctx.data_ptr(),
-                                                            lse.data_ptr(), bits.data_ptr() if use_bits else None,
-                                                            B, L, heads, dh, scale, p, seed, site, s), "fwd")
+        _native.check(abi.forward(lib, qkv, ctx, B, L, heads, mask=mask, lse=lse, bits=bits, scale=scale,
+                                  drop=(p, seed, site)), "fwd")
         dqkv = torch.empty_like(qkv)
-        rc = lib.drt_attention_train_bwd_bits_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(),
-                                                   mask.data_ptr(), bits.data_ptr() if use_bits else None,
-                                                   dqkv.data_ptr(), B, L, heads, dh, scale, p, seed, site, s)
+        rc = abi.backward(lib, qkv, ctx, dctx, lse, dqkv, B, L, heads, mask=mask, bits=bits, scale=scale,
+                          drop=(p, seed, site))
         if L > 160 and not use_bits:
             assert rc != 0
             dqkv = None

@@ -15,6 +15,7 @@ import zlib
 
 import pytest
 
+import attention_abi as abi
 import encoder_refs as er
 
 pytestmark = pytest.mark.gpu
@@ -90,21 +91,18 @@ def _qkv(kind, B, L, heads, mask, g, keep_v=()):
 
 
 def _run_attention(lib, dev, qkv, mask, B, L, heads):
-    """(ctx of drt_attention_bf16, ctx and lse of drt_attention_fwd_lse_bf16) on the CPU.  The
+    """(ctx of drt_attention_forward_bf16 without lse, ctx and lse of the call with it) on the CPU.  The
     outputs start as NaN: an unwritten element fails the finiteness checks."""
     import torch
     from denseretrievaltoolkits_amd import _native
     H = heads * 64
     qd = qkv.to(dev)
     md = None if mask is None else mask.to(dev)
-    mp = None if md is None else md.data_ptr()
     ctx0 = torch.full((B * L, H), float("nan"), dtype=torch.bfloat16, device=dev)
     ctx1 = torch.full_like(ctx0, float("nan"))
     lse = torch.full((B, heads, L), float("nan"), device=dev)
-    s = _native.stream_ptr(dev)
-    _native.check(lib.drt_attention_bf16(qd.data_ptr(), mp, ctx0.data_ptr(), B, L, heads, 64, 0.125, s), "attention")
-    _native.check(lib.drt_attention_fwd_lse_bf16(qd.data_ptr(), mp, ctx1.data_ptr(), lse.data_ptr(), B, L, heads, 64,
-                                                 0.125, s), "attention lse")
+    _native.check(abi.forward(lib, qd, ctx0, B, L, heads, mask=md, scale=0.125), "attention")
+    _native.check(abi.forward(lib, qd, ctx1, B, L, heads, mask=md, lse=lse, scale=0.125), "attention lse")
     torch.cuda.synchronize()
     return ctx0.cpu(), ctx1.cpu(), lse.cpu()
 

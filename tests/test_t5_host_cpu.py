@@ -51,7 +51,11 @@ def test_new_entries_reject_bad_shapes_without_gpu():
     from denseretrievaltoolkits_amd import _native
     lib = _native.load()
     E = _native.DRT_EINVAL
-    att = lib.drt_attention_relbias_bf16
+    att = lib.drt_attention_forward_bf16
+    assert att(None, None, None, None, None, None, 2, 16, 4, 32, 1.0, 0.0, 0, 0, None) == E    # head_dim != 64
+    assert att(None, None, None, None, None, None, 2, 0, 4, 64, 1.0, 0.0, 0, 0, None) == E     # L = 0
+    assert att(None, None, None, None, None, None, 2, 513, 4, 64, 1.0, 0.0, 0, 0, None) == E   # L > 512
+    att = lib.drt_attention_relbias_bf16                                    # the earlier name forwards
     assert att(None, None, None, None, 2, 16, 4, 32, 1.0, None) == E        # head_dim != 64
     assert att(None, None, None, None, 2, 0, 4, 64, 1.0, None) == E         # L = 0
     assert att(None, None, None, None, 2, 513, 4, 64, 1.0, None) == E       # L > 512

@@ -10,6 +10,7 @@ inputs).
 """
 import pytest
 
+import attention_abi as abi
 import t5_refs as tr
 from test_encoder_fwd_fp64_gpu import _ctx_ratio, _gen, _mask, _qkv
 
@@ -85,7 +86,7 @@ def test_t5_embed_exact(dev, B, L, H):
 
 
 # ---------------------------------------------------------------------------------------------
-# drt_attention_relbias_bf16
+# drt_attention_forward_bf16 with relbias
 # ---------------------------------------------------------------------------------------------
 def _table(kind, heads, L, g):
     """fp32 [heads, 2L-1] over k - q, asymmetric: a transposed index or a sign error moves ctx far
@@ -111,15 +112,13 @@ def _soften(qkv, heads):
 
 
 def _run_relbias(lib, dev, qkv, mask, table, B, L, heads, scale=1.0):
-    """ctx of drt_attention_relbias_bf16 on the CPU; the output starts as NaN."""
+    """ctx of drt_attention_forward_bf16 with relbias on the CPU; the output starts as NaN."""
     import torch
     from denseretrievaltoolkits_amd import _native
     qd, td = qkv.to(dev), table.to(dev).contiguous()
     md = None if mask is None else mask.to(dev)
     ctx = torch.full((B * L, heads * 64), float("nan"), dtype=torch.bfloat16, device=dev)
-    _native.check(lib.drt_attention_relbias_bf16(qd.data_ptr(), None if md is None else md.data_ptr(), td.data_ptr(),
-                                                 ctx.data_ptr(), B, L, heads, 64, scale, _native.stream_ptr(dev)),
-                  "attention_relbias")
+    _native.check(abi.forward(lib, qd, ctx, B, L, heads, mask=md, relbias=td, scale=scale), "attention_relbias")
     torch.cuda.synchronize()
     return ctx.cpu()
 
@@ -191,7 +190,7 @@ def test_attention_relbias_fully_masked_row(dev, L):
 @pytest.mark.parametrize("scale", [0.125, 1.0])
 @pytest.mark.parametrize("L", [1, 33, 128, 160, 161, 512])
 def test_attention_relbias_zero_table_bit_identical(dev, L, scale):
-    """An all-zero table gives drt_attention_bf16's bits at the same scale: the variant is the kernel
+    """An all-zero table gives the bits of relbias = NULL at the same scale: the variant is the kernel
     the fp64 suite of tests/test_encoder_fwd_fp64_gpu.py covers."""
     import torch
     from denseretrievaltoolkits_amd import _native
@@ -205,8 +204,7 @@ def test_attention_relbias_zero_table_bit_identical(dev, L, scale):
         qd = qkv.to(dev)
         md = None if mask is None else mask.to(dev)
         want = torch.full((B * L, heads * 64), float("nan"), dtype=torch.bfloat16, device=dev)
-        _native.check(lib.drt_attention_bf16(qd.data_ptr(), None if md is None else md.data_ptr(), want.data_ptr(), B,
-                                             L, heads, 64, scale, _native.stream_ptr(dev)), "attention")
+        _native.check(abi.forward(lib, qd, want, B, L, heads, mask=md, scale=scale), "attention")
         torch.cuda.synchronize()
         assert torch.equal(_bits(got), _bits(want.cpu())), f"L={L} scale={scale} mask={mk}"
 

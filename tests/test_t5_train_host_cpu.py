@@ -1,6 +1,7 @@
 """Host side of the T5 training tower (no GPU): the support check's reasons, the differentiable
 relative-position bias table against autograd through HF's own compute_bias, DRModel's opt-in
 flag, and the new C entries' shape validation."""
+import ctypes
 from types import SimpleNamespace
 
 import pytest
@@ -91,6 +92,28 @@ def test_new_entries_reject_bad_shapes_without_gpu():
     from denseretrievaltoolkits_amd import _native
     lib = _native.load()
     E = _native.DRT_EINVAL
+    fwd = lib.drt_attention_forward_bf16
+    assert fwd(None, None, None, None, None, None, 2, 16, 4, 32, 1.0, 0.0, 0, 0, None) == E     # head_dim
+    assert fwd(None, None, None, None, None, None, 2, 513, 4, 64, 1.0, 0.0, 0, 0, None) == E    # L > 512
+    assert fwd(None, None, None, None, None, None, 2, 16, 4, 64, 1.0, 1.0, 0, 0, None) == E     # p = 1
+    # non-null arguments are the address of a host buffer: nothing is dereferenced before the check
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    bwd = lib.drt_attention_backward_bf16
+    wsq = lib.drt_attention_backward_workspace
+
+    def bwd_rc(relbias=None, dbias=None, dtable=None, ws=None, ws_bytes=0):
+        return bwd(None, None, None, None, None, relbias, None, None, 2, 50, 4, 64, 1.0, 0.0, 0, 0, dbias, dtable,
+                   ws, ws_bytes, None)
+    assert bwd_rc(relbias=p) == E                                                                # no table
+    assert bwd_rc(dtable=p, ws=p, ws_bytes=wsq(2, 50, 4, 64, 1)) == E                            # table, no relbias
+    assert bwd_rc(relbias=p, dbias=p, dtable=p, ws=p, ws_bytes=1 << 30) == E                     # both share ws
+    assert bwd_rc(dbias=p, ws=p, ws_bytes=wsq(2, 50, 4, 64, 0) - 1) == E                         # one byte short
+    assert wsq(2, 513, 4, 64, 1) == 0
+    assert wsq(2, 50, 4, 64, 1) >= 2 * 4 * 99 * 4
+    assert wsq(2, 200, 4, 64, 1) >= 2 * 2 * 4 * 399 * 4                                          # two query groups
+    assert wsq(2, 50, 4, 64, 0) == 2 * 4 * 3 * 256 * 4   # [B][4 groups][3H] fp32; 8 rows need no column-sum scratch
+    # the earlier names forward to the pair: the same refusals and the same sizes
     fwd = lib.drt_attention_relbias_train_fwd_bits_bf16
     assert fwd(None, None, None, None, None, None, 2, 16, 4, 32, 1.0, 0.0, 0, 0, None) == E     # head_dim
     assert fwd(None, None, None, None, None, None, 2, 513, 4, 64, 1.0, 0.0, 0, 0, None) == E    # L > 512
@@ -99,8 +122,9 @@ def test_new_entries_reject_bad_shapes_without_gpu():
     assert bwd(None, None, None, None, None, None, None, None, 2, 16, 4, 64, 1.0, 0.0, 0, 0, None, None, 0,
                None) == E                                                                        # no table
     assert lib.drt_attention_relbias_train_bwd_workspace(2, 513, 4) == 0
-    assert lib.drt_attention_relbias_train_bwd_workspace(2, 50, 4) >= 2 * 4 * 99 * 4
-    assert lib.drt_attention_relbias_train_bwd_workspace(2, 200, 4) >= 2 * 2 * 4 * 399 * 4      # two query groups
+    assert lib.drt_attention_relbias_train_bwd_workspace(2, 50, 4) == wsq(2, 50, 4, 64, 1)
+    assert lib.drt_attention_relbias_train_bwd_workspace(2, 200, 4) == wsq(2, 200, 4, 64, 1)
+    assert lib.drt_attention_train_bwd_bias_workspace(2, 4, 64) == wsq(2, 50, 4, 64, 0)
     assert lib.drt_rmsnorm_bwd_bf16(None, None, None, 1e-6, 4, 320, None, None, None, None, 0, None) == E
     assert lib.drt_rmsnorm_bwd_bf16(None, None, None, 1e-6, 4, 1280, None, None, None, None, 0, None) == E
     assert lib.drt_rmsnorm_bwd_workspace(4, 256) >= 1024 * 256 * 4

@@ -10,6 +10,7 @@ import functools
 
 import pytest
 
+import attention_abi as abi
 import t5_refs as tr
 import t5_train_refs as ttr
 
@@ -157,16 +158,8 @@ def _fwd(lib, dev, qkv, mask, table, B, L, p=0.0, bits=False):
     ctx = torch.empty(B * L, H, dtype=torch.bfloat16, device=dev)
     lse = torch.empty(B, HEADS, L, device=dev)
     kb = torch.zeros(B, HEADS, L, (L + 31) // 32, dtype=torch.int32, device=dev) if bits else None
-    s = _native.stream_ptr(dev)
-    if table is None:
-        _native.check(lib.drt_attention_train_fwd_bits_bf16(qkv.data_ptr(), mask.data_ptr(), ctx.data_ptr(),
-                                                            lse.data_ptr(), kb.data_ptr() if bits else None, B, L,
-                                                            HEADS, 64, 1.0, p, SEED, SITE, s), "fwd")
-    else:
-        _native.check(lib.drt_attention_relbias_train_fwd_bits_bf16(qkv.data_ptr(), mask.data_ptr(), table.data_ptr(),
-                                                                    ctx.data_ptr(), lse.data_ptr(),
-                                                                    kb.data_ptr() if bits else None, B, L, HEADS, 64,
-                                                                    1.0, p, SEED, SITE, s), "relbias train fwd")
+    _native.check(abi.forward(lib, qkv, ctx, B, L, HEADS, mask=mask, relbias=table, lse=lse, bits=kb, scale=1.0,
+                              drop=(p, SEED, SITE)), "fwd")
     return ctx, lse, kb
 
 
@@ -174,21 +167,15 @@ def _bwd(lib, dev, qkv, ctx, dctx, lse, mask, table, kb, B, L, p=0.0):
     import torch
     from denseretrievaltoolkits_amd import _native
     dqkv = torch.zeros_like(qkv)
-    s = _native.stream_ptr(dev)
     if table is None:
-        _native.check(lib.drt_attention_train_bwd_bits_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
-                                                            lse.data_ptr(), mask.data_ptr(),
-                                                            kb.data_ptr() if kb is not None else None, dqkv.data_ptr(),
-                                                            B, L, HEADS, 64, 1.0, p, SEED, SITE, s), "bwd")
+        _native.check(abi.backward(lib, qkv, ctx, dctx, lse, dqkv, B, L, HEADS, mask=mask, bits=kb, scale=1.0,
+                                   drop=(p, SEED, SITE)), "bwd")
         return dqkv, None
-    nb = int(lib.drt_attention_relbias_train_bwd_workspace(B, L, HEADS))
+    nb = int(lib.drt_attention_backward_workspace(B, L, HEADS, 64, 1))
     ws = torch.empty((nb + 3) // 4, device=dev)
     dtable = torch.full((HEADS, 2 * L - 1), float("nan"), device=dev)
-    _native.check(lib.drt_attention_relbias_train_bwd_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
-                                                           lse.data_ptr(), mask.data_ptr(), table.data_ptr(),
-                                                           kb.data_ptr() if kb is not None else None, dqkv.data_ptr(),
-                                                           B, L, HEADS, 64, 1.0, p, SEED, SITE, dtable.data_ptr(),
-                                                           ws.data_ptr(), nb, s), "relbias train bwd")
+    _native.check(abi.backward(lib, qkv, ctx, dctx, lse, dqkv, B, L, HEADS, mask=mask, relbias=table, bits=kb,
+                               scale=1.0, drop=(p, SEED, SITE), dtable=dtable, ws=ws, ws_bytes=nb), "relbias bwd")
     return dqkv, dtable
 
 
@@ -210,7 +197,7 @@ def _check_grads(tag, dqkv, dtable, want_dqkv, want_dtable):
 
 @pytest.mark.parametrize("B,L", ATT_CASES)
 def test_relbias_train_fwd(dev, B, L):
-    """At p = 0 ctx has drt_attention_relbias_bf16's bits; lse against fp64."""
+    """At p = 0 ctx has the bits of the inference call (no lse, no dropout arguments); lse against fp64."""
     import torch
     from denseretrievaltoolkits_amd import _native
     lib = _native.load()
@@ -218,8 +205,7 @@ def test_relbias_train_fwd(dev, B, L):
     qkv, mask, table = c["qkv"].to(dev), c["mask"].to(dev), c["table"].to(dev)
     ctx, lse, _ = _fwd(lib, dev, qkv, mask, table, B, L)
     ctx0 = torch.empty_like(ctx)
-    _native.check(lib.drt_attention_relbias_bf16(qkv.data_ptr(), mask.data_ptr(), table.data_ptr(), ctx0.data_ptr(), B,
-                                                 L, HEADS, 64, 1.0, _native.stream_ptr(dev)), "relbias fwd")
+    _native.check(abi.forward(lib, qkv, ctx0, B, L, HEADS, mask=mask, relbias=table, scale=1.0), "relbias fwd")
     torch.cuda.synchronize()
     assert torch.equal(ctx.view(torch.int16), ctx0.view(torch.int16))
     torch.testing.assert_close(lse.double().cpu(), c["lse"], atol=1e-3, rtol=1e-4)
@@ -261,7 +247,7 @@ def test_dtable_is_zero_under_masked_and_padded_keys(dev, B, L):
 @pytest.mark.parametrize("p", [0.0, P])
 @pytest.mark.parametrize("B,L", ATT_CASES)
 def test_zero_table_gives_the_plain_kernels_bits(dev, B, L, p):
-    """With an all-zero table dQKV equals drt_attention_train_bwd_bits_bf16's bit for bit: without
+    """With an all-zero table dQKV equals the bits of relbias = NULL: without
     dropout, on the keep-bits path and (L <= 160, where the plain kernel has it) on the hashed path."""
     import torch
     from denseretrievaltoolkits_amd import _native

@@ -1,4 +1,4 @@
-"""Attention forward A/B, one library per process (DRT_LIB=<variant>): drt_attention_bf16 at the encode
+"""Attention forward A/B, one library per process (DRT_LIB=<variant>): drt_attention_forward_bf16 at the encode
 leg's half batch (256 x 128 x 12 heads; all-ones and ragged masks), the query tower's (128 x 32) and a
 ragged 64 x 100 -- HIP-event us per launch and an output digest -- then the encode leg (passages/s)."""
 import json
@@ -31,8 +31,9 @@ def main(reps=50):
             lens = torch.randint(L // 4, L + 1, (B,), generator=g, device=dev)
             mask = (torch.arange(L, device=dev)[None, :] < lens[:, None]).to(torch.int64)
         ctx = torch.empty((B * L, H), dtype=torch.bfloat16, device=dev)
-        run = lambda: _native.check(lib.drt_attention_bf16(qkv.data_ptr(), mask.data_ptr(), ctx.data_ptr(), B, L,
-                                                           heads, dh, 1.0 / math.sqrt(dh), st), "attn")
+        run = lambda: _native.check(lib.drt_attention_forward_bf16(qkv.data_ptr(), mask.data_ptr(), None, ctx.data_ptr(),
+                                                                   None, None, B, L, heads, dh, 1.0 / math.sqrt(dh),
+                                                                   0.0, 0, 0, st), "attn")
         run()
         torch.cuda.synchronize()
         ts = []

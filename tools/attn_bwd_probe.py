@@ -32,13 +32,13 @@ def main(reps=10, shapes=((1024, 128), (1024, 156), (512, 32))):
             bp = bits.data_ptr() if use_bits else None
 
             def fwd():
-                return lib.drt_attention_train_fwd_bits_bf16(qkv.data_ptr(), mask.data_ptr(), ctx.data_ptr(),
-                                                             lse.data_ptr(), bp, B, L, heads, 64, 0.125, p, 123, 4, s)
+                return lib.drt_attention_forward_bf16(qkv.data_ptr(), mask.data_ptr(), None, ctx.data_ptr(),
+                                                      lse.data_ptr(), bp, B, L, heads, 64, 0.125, p, 123, 4, s)
 
             def bwd():
-                return lib.drt_attention_train_bwd_bits_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
-                                                             lse.data_ptr(), mask.data_ptr(), bp, dqkv.data_ptr(), B,
-                                                             L, heads, 64, 0.125, p, 123, 4, s)
+                return lib.drt_attention_backward_bf16(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(),
+                                                       lse.data_ptr(), mask.data_ptr(), None, bp, dqkv.data_ptr(), B,
+                                                       L, heads, 64, 0.125, p, 123, 4, None, None, None, 0, s)
             tag = "" if p == 0 else ("_bits" if use_bits else "_hash")
             for name, fn in (("fwd", fwd), ("bwd", bwd)):
                 _native.check(fn(), name)

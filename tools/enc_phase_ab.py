@@ -76,9 +76,9 @@ def main(rounds=3, steps=8, B=512):
                     enc._ws = None
                     ops = [
                         lambda: enc._lin(h, ly["wqkv"], ly["bqkv"], bf["qkv"]),
-                        lambda: _native.check(enc.lib.drt_attention_bf16(
-                            bf["qkv"].data_ptr(), mask[a:b].data_ptr(), bf["ctx"].data_ptr(), b - a, L, sh.heads,
-                            H // sh.heads, scale, enc.stream), "attn"),
+                        lambda: _native.check(enc.lib.drt_attention_forward_bf16(
+                            bf["qkv"].data_ptr(), mask[a:b].data_ptr(), None, bf["ctx"].data_ptr(), None, None, b - a, L,
+                            sh.heads, H // sh.heads, scale, 0.0, 0, 0, enc.stream), "attn"),
                         lambda: enc._lin_ln(bf["ctx"], ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], bf["x32"],
                                             enc.lib.drt_layernorm_bf16),
                         lambda: enc._lin(h, ly["wi"], ly["bi"], bf["ffn"], gelu=True),
