@@ -10,7 +10,9 @@
 //                   tiles; S^T = K Q^T keeps each query's scores lane-local and
 //                   the S^T accumulator feeds the P.V MFMA directly as its B
 //                   operand (no LDS round trip for P); the RB instantiations add T5's
-//                   relative-position bias to the scores (drt_attention_forward_bf16, relbias)
+//                   relative-position bias to the scores (drt_attention_forward_bf16, relbias);
+//                   the VL instantiations read each sequence's rows from a sequence-offset
+//                   table (packed batches, drt_attention_varlen_forward_bf16; csrc/packed.hip)
 //   pool            first / masked-mean / masked-max pooling (utils.py:233-240)
 //   l2norm          F.normalize(reps, dim=1) (biencoder.py:149-150)
 #include "drt_common.h"
@@ -220,6 +222,10 @@ struct AttnArgs {
                           //   (query, key >> 5) -- the backward reads it instead of re-hashing
   const float* relbias;   // RB kernels: [heads][2 L - 1] fp32, entry (head, key - query + L - 1) is added
                           //   to the score of (query, key) before the softmax (T5's relative-position bias)
+  // VL kernels (packed batches, drt_attention_varlen_forward_bf16): qkv / ctx hold T = cu[B] token rows
+  const int32_t* cu_seqlens;  // [B + 1] row offsets of the sequences; B, L, mask, lse and the dropout fields unused
+  const int32_t* seq_ids;     // [n_seqs] the sequences this launch covers, or null: 0 .. n_seqs - 1
+  int max_len;                // bound of every listed length (the launch's LDS image); longer ones are clamped
 };
 
 // Attention forward, one work-group per (sequence, head): K (swizzled rows), V^T and the key bias
@@ -250,13 +256,25 @@ constexpr float kLn2 = 0.6931471805599453f;
 // so the 32 query rows of each half of a wave read consecutive banks.  The bias joins kb before the
 // fma: a masked key stays at -FLT_MAX (the bias is absorbed, as in HF's fp32 sum), a padding key at
 // -inf, and an all-zero table leaves every bit of the !RB kernel's result.
-template <int NB, bool DROP, bool RB = false>
+// VL (packed inference batches, csrc/packed.hip): the work-group's sequence is seq_ids[blockIdx.x / heads]
+// (or that index itself), its rows start at cu[b] and its length is cu[b + 1] - cu[b], read per
+// work-group; no mask (a packed sequence has no masked keys: kb is 0 below len, -inf in the tile
+// padding), no lse, no dropout.  NB is the launch's length class: every listed len <= 32 NB.
+template <int NB, bool DROP, bool RB = false, bool VL = false>
 __global__ __launch_bounds__(NB == 5 ? 320 : 256) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void attention_fwd_kernel(AttnArgs a) {
   constexpr int NW = NB == 5 ? 5 : 4;
   constexpr int NT = NW * 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int L = (int)a.L;
+  const int64_t b = VL ? (a.seq_ids ? a.seq_ids[blockIdx.x / a.heads] : blockIdx.x / a.heads) : blockIdx.x / a.heads;
+  const int64_t row0 = VL ? a.cu_seqlens[b] : b * a.L;
+  int Lv = 0;
+  if (VL) {   // clamped to the launch's bound: a wrong table cannot run past the LDS image
+    Lv = a.cu_seqlens[b + 1] - (int)row0;
+    Lv = Lv < a.max_len ? Lv : a.max_len;
+    if (Lv <= 0) return;                    // the whole work-group: no barrier is left waiting
+  }
+  const int L = VL ? Lv : (int)a.L;
   const int Lp = NB ? NB * 32 : (L + 31) & ~31;  // keys padded to the 32-key tile
   const int nqb = Lp / 32;
   const int vts = Lp * 2 + 8;              // Vt row stride (bytes): conflict-free ds_read_b64
@@ -268,9 +286,7 @@ void attention_fwd_kernel(AttnArgs a) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
-  const int64_t b = blockIdx.x / a.heads;
   const int hd = blockIdx.x % a.heads;
-  const int64_t row0 = b * a.L;
   const int64_t hrow = ((int64_t)b * a.heads + hd) * L;
   const int64_t ld = 3 * (int64_t)a.H;
   const __bf16* Qg = a.qkv + row0 * ld + hd * kHeadDim;
@@ -323,7 +339,7 @@ void attention_fwd_kernel(AttnArgs a) {
   for (int i = tid; i < Lp; i += NT) {
     float bv = 0.0f;
     if (i >= L) bv = -__builtin_inff();   // tile padding: P exactly 0, in a row of masked keys too
-    else if (a.mask && a.mask[b * a.L + i] == 0) bv = -3.402823466e+38f;  // (1 - mask) * finfo.min
+    else if (!VL && a.mask && a.mask[b * a.L + i] == 0) bv = -3.402823466e+38f;  // (1 - mask) * finfo.min
     kb[i] = bv;
   }
   if (RB) {
@@ -342,8 +358,10 @@ void attention_fwd_kernel(AttnArgs a) {
   const float inv = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
   const uint32_t thr = DROP ? attn_drop_threshold(a.drop_p) : 0u;
   bf16x8 oo[2][2];                           // NB: this wave's O block, [t][g / 2] (bf16)
+  // VL: a sequence shorter than its class skips the query blocks and key tiles that hold no token
+  const int nqv = VL ? (L + 31) >> 5 : nqb;
 
-  for (int qb = wave; qb < nqb; qb += NW) {
+  for (int qb = wave; qb < nqb && (!VL || qb < nqv); qb += NW) {
     // Q fragment (B operand, B[k=d][col=q] = Q[q][d]) scaled by 1/sqrt(dh)
     const int qq = qb * 32 + r;
     const int qrow = qq < L ? qq : L - 1;
@@ -465,7 +483,8 @@ void attention_fwd_kernel(AttnArgs a) {
     };
     if (NB) {
 #pragma unroll
-      for (int j = 0; j < (NB ? NB : 1); ++j) tile(32 * j);
+      for (int j = 0; j < (NB ? NB : 1); ++j)
+        if (!VL || j < nqv) tile(32 * j);
       if (DROP && a.drop_bits && h == 0 && qq < L) {   // the row's words: contiguous over the wave's queries
         uint32_t* dst = a.drop_bits + (hrow + qq) * nqb;
         if (NB == 4) {
@@ -479,7 +498,7 @@ void attention_fwd_kernel(AttnArgs a) {
       for (int kt = 0; kt < Lp; kt += 32) tile(kt);
     }
     // O^T[d][q]: lane holds query r; d = 32t + (e&3) + 8(e>>2) + 4h
-    if (qq < L && a.lse && h == 0) a.lse[hrow + qq] = (m + __log2f(l)) * kLn2;
+    if (!VL && qq < L && a.lse && h == 0) a.lse[hrow + qq] = (m + __log2f(l)) * kLn2;
     const float sc = inv / l;
     if (NB) {
 #pragma unroll
@@ -502,7 +521,7 @@ void attention_fwd_kernel(AttnArgs a) {
   if (NB) {
     // O through LDS (the K image, dead once every wave is past its last tile): rows of 128 B
     __syncthreads();
-    if (wave < nqb) {
+    if (wave < nqv) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -705,6 +724,38 @@ int drt_attention_forward_bf16(const void* qkv, const int64_t* mask, const float
   }
   void* args[] = {&a};
   hipLaunchKernel((const void*)kernels[nb][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
+                  (hipStream_t)stream);
+  return hip_status(hipGetLastError());
+}
+
+// The forward over a packed batch (contract: drt.h): the VL instantiations, one work-group per
+// (listed sequence, head).  max_len picks the instantiation and sizes the LDS image, so a launch
+// over one length class keeps that class's occupancy whatever the batch's longest sequence is.
+int drt_attention_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                      int64_t n_seqs, int32_t max_len, void* ctx, int32_t heads, int32_t head_dim,
+                                      float scale, void* stream) {
+  DRT_REQUIRE(n_seqs >= 0 && max_len > 0 && max_len <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(n_seqs * heads < (1ll << 31));
+  if (n_seqs == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && cu_seqlens && ctx);
+  AttnArgs a{(const __bf16*)qkv, nullptr, (__bf16*)ctx, 0, 0, heads, heads * head_dim, scale, nullptr, 0.0f, 0, 0,
+             nullptr, nullptr, cu_seqlens, seq_ids, max_len};
+  using Kernel = void (*)(AttnArgs);
+  static constexpr Kernel kernels[6] = {
+      attention_fwd_kernel<0, false, false, true>, attention_fwd_kernel<1, false, false, true>,
+      attention_fwd_kernel<2, false, false, true>, attention_fwd_kernel<3, false, false, true>,
+      attention_fwd_kernel<4, false, false, true>, attention_fwd_kernel<5, false, false, true>};
+  const int Lp = ((int)max_len + 31) & ~31;
+  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;
+  static bool attr_set = false;
+  if (!attr_set) {   // max_len > 224 stages more than the default 64 KiB
+    for (const Kernel k : kernels)
+      DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  void* args[] = {&a};
+  hipLaunchKernel((const void*)kernels[nb], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
                   (hipStream_t)stream);
   return hip_status(hipGetLastError());
 }

@@ -9,7 +9,11 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   kernels (model/encoder.HipBertEncoder): bf16 MFMA GEMMs, fused attention, fp32
   LayerNorm statistics, pooling / head / L2-normalise kernels.  ``hidden`` is
   returned in bf16, ``reps`` in fp32.  ``encoder_only`` T5 towers (T5EncoderModel)
-  take the same path through model/t5_encoder.HipT5Encoder.
+  take the same path through model/t5_encoder.HipT5Encoder.  With ``hip_packed = True``
+  (attribute, or ``model_args.hip_packed``; default off) a BERT tower computes only the real
+  tokens of a padded batch (model/packing.py, HipBertEncoder.forward_packed): ``reps`` as
+  before, ``hidden`` [B, L, H] with ZEROS at the pad positions.  A mask that is not a batch of
+  non-empty prefixes, a batch with too little padding and T5 towers keep the padded path.
 * encode with autograd (training, or eval mode with grad on, where the reference
   returns differentiable reps) runs BERT towers up to L = 512 on the HIP training
   tower (model/train_tower.py: forward with saved bf16 activations + backward on
@@ -42,6 +46,7 @@ from transformers import AutoModel, BatchEncoding, PreTrainedModel
 from transformers.modeling_outputs import ModelOutput
 
 from .encoder import HipBertEncoder, l2_normalize_, linear_head
+from .packing import plan_packing
 from .t5_encoder import HipT5Encoder, t5_supported
 from .train_tower import MAX_TRAIN_SEQ, tower_supported, train_hidden
 from .t5_train_tower import t5_tower_supported, train_hidden_t5
@@ -67,6 +72,22 @@ def _log_fallback(why: str):
     if why not in _FALLBACK_LOGGED:
         _FALLBACK_LOGGED.add(why)
         logger.warning("DRModel.encode: HF module under torch, not the HIP tower (%s)", why)
+
+
+def packed_plan(enc, items):
+    """The packing plan of a batch for an encode with ``hip_packed`` set, or None (padded path, the
+    reason logged once): the tower is not a HipBertEncoder (T5 stays padded), or the mask is not a
+    batch of non-empty prefixes with padding to drop (model/packing.py)."""
+    if not isinstance(enc, HipBertEncoder):
+        _log_fallback(f"hip_packed: padded path, {type(enc).__name__} has no packed form")
+        return None
+    ids = items["input_ids"]
+    plan = plan_packing(items.get("attention_mask"), ids.shape[1], device=enc.device)
+    if plan is None or plan.B != ids.shape[0]:
+        _log_fallback("hip_packed: padded path, the mask is not a batch of non-empty prefixes with "
+                      "enough padding to drop")
+        return None
+    return plan
 
 
 def _torch_mean_pooling(h, mask):
@@ -96,6 +117,9 @@ class DRModel(nn.Module):
         self.hip_train = True   # HIP training tower for BERT towers with L <= 512 (set False: HF autograd)
         # opt-in: T5EncoderModel towers with autograd on the HIP T5 training tower (default: HF module)
         self.hip_train_t5 = bool(getattr(model_args, "hip_train_t5", False))
+        # opt-in: padding-free inference of BERT towers (only the real tokens of a padded batch are
+        # computed; model/packing.py, HipBertEncoder.forward_packed)
+        self.hip_packed = bool(getattr(model_args, "hip_packed", False))
         self.normalize = normalize
         self.model_args = model_args
         self.train_args = train_args
@@ -211,8 +235,18 @@ class DRModel(nn.Module):
         # it takes the HF module below, with the reason logged, whether or not autograd is on
         if self._use_hip(model) and self.feature == "last_hidden_state":
             enc = self._hip_encoder(model)
-            hidden = enc(items["input_ids"], items.get("attention_mask"), items.get("token_type_ids"))
-            reps, rb = enc.pool(hidden, items.get("attention_mask"), self.pooling, want_bf16=head is not None)
+            plan = packed_plan(enc, items) if self.hip_packed else None
+            if plan is not None:
+                # padding-free: only the real tokens are computed; `hidden` comes back in the padded
+                # [B, L, H] layout with ZEROS at the pad positions (the padded path leaves the
+                # encoder's values of the pad tokens there, which the reference never reads)
+                L = items["input_ids"].shape[1]
+                packed = enc.forward_packed(items["input_ids"], plan, items.get("token_type_ids"))
+                reps, rb = enc.pool_packed(packed, plan, L, self.pooling, want_bf16=head is not None)
+                hidden = enc.unpack(packed, plan, L)
+            else:
+                hidden = enc(items["input_ids"], items.get("attention_mask"), items.get("token_type_ids"))
+                reps, rb = enc.pool(hidden, items.get("attention_mask"), self.pooling, want_bf16=head is not None)
             if head is not None:
                 reps = linear_head(rb, self._head_weight(head))
             if self.normalize:

@@ -82,6 +82,13 @@ class HipBertEncoder:
         # from 8192 tokens: 256 x 32-token queries 2.47 -> 2.06 ms, 512 x 32 3.81 -> 3.74 (4096 tokens:
         # slower, 1.36 -> 1.50; tools/qenc_split_ab.py, profiles/r03zc_qenc_split_ab.log)
         self.split_min_tokens = 8192
+        # forward_packed switches, both off by measurement (tools/packed_encode_ab.py,
+        # profiles/packed01/packed_encode_ab.json): one attention launch per length class was slower
+        # than one launch per batch at every shape (a layer's attention 64 vs 49 us at 512 x 128), and
+        # two halves on two streams from split_min_tokens real tokens up lost at three shapes of four
+        # (8.41 vs 8.26 ms at 512 x 128; 256 x 160 gained 4 %)
+        self.packed_classes = False
+        self.packed_split_streams = False
         self._streams = None
         self._ws_plan = {}
         self._ws = None
@@ -277,6 +284,103 @@ class HipBertEncoder:
         return h.view(B, L, H)
 
     __call__ = forward
+
+    # -- padding-free inference ---------------------------------------------
+    # Only the T real tokens of the batch are computed (model/packing.py): the layer loop of _run
+    # over [T, H] matrices, with the packed embedding and the varlen attention (one launch per
+    # length class of the plan, so a long sequence does not set the short ones' LDS footprint).  No
+    # graph replay.
+    def forward_packed(self, input_ids: torch.Tensor, plan, token_type_ids: Optional[torch.Tensor] = None
+                       ) -> torch.Tensor:
+        """last_hidden_state of the real tokens, [T, H] bf16 in the plan's packed order."""
+        dev = self.device
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        B, L = ids.shape
+        if (B, L) != (plan.B, plan.L):
+            raise ValueError(f"plan of a [{plan.B}, {plan.L}] batch used with input_ids [{B}, {L}]")
+        if L > self.pos.shape[0]:
+            raise ValueError(f"sequence length {L} exceeds max_position_embeddings {self.pos.shape[0]}")
+        tt = token_type_ids.to(dev, torch.int64).contiguous() if token_type_ids is not None else None
+        if (self.packed_split_streams and B >= 2 and plan.T >= self.split_min_tokens
+                and not torch.cuda.is_current_stream_capturing()):
+            return self._run_packed_halves(ids, plan, tt)
+        return self._run_packed(ids, plan, tt)
+
+    def _run_packed_halves(self, ids, plan, tt):
+        dev = self.device
+        out = torch.empty((plan.T, self.shape.hidden), dtype=torch.bfloat16, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        if self._streams is None:
+            self._streams = [torch.cuda.Stream(dev) for _ in range(2)]
+        row = 0
+        for st, (b0, sub) in zip(self._streams, plan.halves()):
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                self._run_packed(ids[b0:b0 + sub.B], sub, tt[b0:b0 + sub.B] if tt is not None else None,
+                                 out=out[row:row + sub.T])
+            out.record_stream(st)
+            row += sub.T
+        for st in self._streams:
+            cur.wait_stream(st)
+        return out
+
+    def _run_packed(self, ids, plan, tt, out=None):
+        sh = self.shape
+        dev = self.device
+        B, L = ids.shape
+        H, T = sh.hidden, plan.T
+        self.stream = _native.stream_ptr(dev)
+        cu = plan.cu_seqlens.data_ptr()
+        h = out if out is not None else torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        _native.check(self.lib.drt_embed_ln_packed(ids.data_ptr(), tt.data_ptr() if tt is not None else None, cu, B, L, T,
+                                                   self.word.data_ptr(), self.pos.data_ptr(), self.type.data_ptr(),
+                                                   self.emb_g.data_ptr(), self.emb_b.data_ptr(), sh.eps, H,
+                                                   h.data_ptr(), self.stream), "drt_embed_ln_packed")
+        qkv = torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev)
+        ctx = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        f32 = self.presum == "fp32"
+        x32 = torch.empty((T, H), dtype=torch.float32 if f32 else torch.bfloat16, device=dev)
+        ln = self.lib.drt_layernorm_f32_bf16 if f32 else self.lib.drt_layernorm_bf16
+        ffn = torch.empty((T, sh.intermediate), dtype=torch.bfloat16, device=dev)
+        nb = self._ws_bytes(T)
+        self._ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev) if nb else None
+        scale = 1.0 / math.sqrt(H // sh.heads)
+        launches = plan.classes() if self.packed_classes else [(None, B, plan.max_len)]
+        launches = [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]
+        for ly in self.layers:
+            self._lin(h, ly["wqkv"], ly["bqkv"], qkv)
+            for sp, n, ml in launches:
+                _native.check(self.lib.drt_attention_varlen_forward_bf16(qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(),
+                                                                         sh.heads, H // sh.heads, scale, self.stream),
+                              "drt_attention_varlen_forward_bf16")
+            self._lin_ln(ctx, ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], x32, ln)
+            self._lin(h, ly["wi"], ly["bi"], ffn, gelu=True)
+            self._lin_ln(ffn, ly["wf"], ly["bf"], h, ly["g2"], ly["b2"], x32, ln)
+        return h
+
+    def pool_packed(self, hidden: torch.Tensor, plan, L: int, pooling: str, want_bf16: bool = False):
+        """pool() over a packed [T, H] hidden state: the same reps (max pooling keeps the reference's
+        max(hidden * mask), 0 where a sequence is shorter than L)."""
+        if pooling not in POOL_MODES:
+            raise ValueError("Unknown pooling type: {}".format(pooling))
+        T, H = hidden.shape
+        dev = hidden.device
+        reps = torch.empty((plan.B, H), dtype=torch.float32, device=dev)
+        rb = torch.empty((plan.B, H), dtype=torch.bfloat16, device=dev) if want_bf16 else None
+        _native.check(self.lib.drt_pool_packed_bf16(hidden.data_ptr(), plan.cu_seqlens.data_ptr(), plan.B, L, H,
+                                                    POOL_MODES[pooling], reps.data_ptr(),
+                                                    rb.data_ptr() if rb is not None else None,
+                                                    _native.stream_ptr(dev)), "drt_pool_packed_bf16")
+        return reps, rb
+
+    def unpack(self, hidden: torch.Tensor, plan, L: int) -> torch.Tensor:
+        """[B, L, H] bf16 from packed [T, H]: the real tokens at their positions, zeros at the pads."""
+        T, H = hidden.shape
+        out = torch.empty((plan.B, L, H), dtype=torch.bfloat16, device=hidden.device)
+        _native.check(self.lib.drt_unpack_rows_bf16(hidden.data_ptr(), plan.cu_seqlens.data_ptr(), plan.B, L, H,
+                                                    out.data_ptr(), _native.stream_ptr(hidden.device)),
+                      "drt_unpack_rows_bf16")
+        return out
 
     def pool(self, hidden: torch.Tensor, attention_mask: Optional[torch.Tensor], pooling: str,
              want_bf16: bool = False):

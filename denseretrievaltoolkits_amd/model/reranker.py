@@ -7,7 +7,9 @@ tower runs on the HIP inference kernels (the same bf16 MFMA GEMMs + fused
 attention as the bi-encoder) and the 768 -> 1 head on the HIP GEMM; with grad on
 (training, or eval mode with grad) BERT pair towers up to L = 512 run on the HIP
 training tower (model/train_tower.py, forward + backward on HIP kernels, HF
-train-mode dropout), other towers on the HF module under autograd.
+train-mode dropout), other towers on the HF module under autograd.  ``hip_packed = True``
+(attribute, or ``model_args.hip_packed``) makes the no-grad BERT pair tower padding-free: only
+the pairs' real tokens are computed (model/packing.py); same scores up to bf16 rounding.
 
 T5 rerankers (monoT5, :115-119: ``T5ForConditionalGeneration`` with ``decoder_input_ids = 0``,
 scores = ``logits[:, 0, [neg_token_id, pos_token_id]]``) follow the same rule: with no gradient to
@@ -73,6 +75,8 @@ class RRModel(nn.Module):
         self.data_args = data_args
         self.train_args = train_args
         self._hip = None
+        # opt-in: padding-free inference of a BERT pair tower (model/packing.py); T5 rerankers stay padded
+        self.hip_packed = bool(getattr(model_args, "hip_packed", False))
         if train_args is not None:
             self.loss_fn_str = train_args.loss_fn
             self.margin = train_args.margin
@@ -135,6 +139,9 @@ class RRModel(nn.Module):
             return None, None
         items = BatchEncoding(items)
         if "T5" in type(self.lm).__name__ and not getattr(self.model_args, "encoder_only", False):
+            if self.hip_packed:
+                from .biencoder import _log_fallback
+                _log_fallback("hip_packed: padded path, a T5 reranker has no packed form")
             return self._encode_t5(items)
         if self.pooling not in ("first", "mean"):
             raise ValueError("Unknown pooling type: {}".format(self.pooling))
@@ -145,6 +152,14 @@ class RRModel(nn.Module):
         if dev.type == "cuda" and (not torch.is_grad_enabled() or frozen):
             enc, w = self._hip_state()
             mask = items.get("attention_mask")
+            plan = None
+            if self.hip_packed:   # padding-free: only the pairs' real tokens are computed
+                from .biencoder import packed_plan
+                plan = packed_plan(enc, items)
+            if plan is not None:
+                packed = enc.forward_packed(items["input_ids"], plan, items.get("token_type_ids"))
+                _, rb = enc.pool_packed(packed, plan, items["input_ids"].shape[1], self.pooling, want_bf16=True)
+                return linear_head(rb, w)
             hidden = enc(items["input_ids"], mask, items.get("token_type_ids"))
             _, rb = enc.pool(hidden, mask, self.pooling, want_bf16=True)
             return linear_head(rb, w)  # [B, 1] fp32

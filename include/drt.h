@@ -574,6 +574,41 @@ int drt_pool_bf16(const void* hidden, const int64_t* mask, int64_t B, int64_t L,
                   int32_t mode, float* out, void* out_bf16, void* stream);
 int drt_l2_normalize_f32(float* x, int64_t B, int32_t H, void* out_bf16, void* stream);
 /* ------------------------------------------------------------------------
+ * Padding-free ("packed") BERT inference: only the T = sum of len_b real tokens of a batch are
+ * computed, as one [T, H] matrix (sequence b's rows at cu_seqlens[b] .. cu_seqlens[b + 1] - 1, in
+ * position order).  cu_seqlens is int32 [B + 1] on the device, cu[0] = 0, cu[B] = T, non-decreasing.
+ * The linears and LayerNorms above take M = T rows as they are; the four entries below replace the
+ * ones that know the [B, L] rectangle.  Inference only (no lse, dropout or backward); a bad argument
+ * is DRT_EINVAL before any HIP call, an empty input (B, n_seqs or T of 0) DRT_OK.
+ * ------------------------------------------------------------------------
+ * drt_embed_ln_packed: out [T, H] bf16; packed row t of sequence b reads ids / type_ids (padded
+ *   [B, L], type_ids may be NULL) at b * L + (t - cu[b]) and position row t - cu[b].  Each row has
+ *   the bits of drt_embed_ln's row for the same token.  H % 256 == 0, H <= 1024, T <= B * L.
+ * drt_attention_varlen_forward_bf16: ctx [T, H] bf16 = softmax(Q K^T * scale) V per (sequence, head)
+ *   from packed qkv [T, 3H], for the n_seqs sequences listed in seq_ids (int32, device; NULL =
+ *   sequences 0 .. n_seqs - 1); rows of unlisted sequences are not touched.  Every listed sequence
+ *   must have 1 <= len <= max_len <= 512: max_len selects the kernel (ceil(max_len / 32) <= 5 key
+ *   blocks held in registers, else the streamed form) and sizes its LDS, so the host may launch one
+ *   length class per call.  A length above max_len is clamped to it (the tail rows are not
+ *   written), a length below 1 writes nothing.  No mask: a packed sequence has no masked keys.
+ *   head_dim == 64, H = heads * 64.
+ * drt_pool_packed_bf16: reps fp32 [B, H] (+ optional bf16 copy) from hidden [T, H]: mode 0 row
+ *   cu[b]; 1 the fp32 sequential sum of the len rows / len; 2 their max, and 0 where len < L (the
+ *   reference's max(hidden * mask) sees a 0 at every pad position; drt_pool_bf16 does the same).
+ * drt_unpack_rows_bf16: out [B * L, H] bf16 = each sequence's rows at b * L .., zeros at the pad
+ *   positions.  H % 8 == 0, packed and out 16-byte aligned.                                      */
+int drt_embed_ln_packed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, int64_t B,
+                        int64_t L, int64_t T, const float* word_emb, const float* pos_emb,
+                        const float* type_emb, const float* gamma, const float* beta, float eps, int32_t H,
+                        void* out, void* stream);
+int drt_attention_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                      int64_t n_seqs, int32_t max_len, void* ctx, int32_t heads,
+                                      int32_t head_dim, float scale, void* stream);
+int drt_pool_packed_bf16(const void* hidden, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H,
+                         int32_t mode, float* out, void* out_bf16, void* stream);
+int drt_unpack_rows_bf16(const void* packed, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H,
+                         void* out, void* stream);
+/* ------------------------------------------------------------------------
  * T5 encoder forward building blocks (HF T5EncoderModel in eval mode, modeling_t5.py; pre-norm
  * layer = rmsnorm -> linear(QKV, no bias) -> attention + relative bias -> linear(out, +residual)
  * -> rmsnorm -> linear(FFN1, ReLU | gated gelu_new) -> linear(FFN2, +residual); final rmsnorm).
