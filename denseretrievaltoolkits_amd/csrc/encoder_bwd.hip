@@ -25,8 +25,8 @@ __device__ __forceinline__ float bwd_wave_sum(float v) {
 constexpr int kLnBwdBlocks = 1024;   // grid of the row pass = rows of the parameter-gradient partials
 
 // One wave per row (grid-stride over rows), H = 64 * EPL; lane owns columns
-// (e / 4) * 256 + lane * 4 + e % 4.  Statistics recomputed from the stored bf16 pre-LN sums
-// exactly as layernorm_bf16_kernel computed them.  Each block leaves its dgamma / dbeta
+// (e / 4) * 256 + lane * 4 + e % 4.  Statistics recomputed from the stored bf16 pre-LN sums (two
+// passes over the row shifted by its first element).  Each block leaves its dgamma / dbeta
 // partial sums in part[blockIdx.x][0..H) and part[gridDim.x + blockIdx.x][0..H); SUM: also the
 // column sums of the gradient handed down (dxd when dropping, else dx, as stored in bf16) in
 // part[2 gridDim.x + blockIdx.x] -- the bias gradient of the linear below, without a pass
@@ -64,9 +64,16 @@ __global__ __launch_bounds__(256, EPL <= 12 ? 4 : 1) void layernorm_bwd_kernel(c
         if (SUM) gmr[SUM ? e4 * 4 + u : 0] = g4[u];
       }
     }
+    // the row shifted by its first element (exact for bf16 values of like magnitude): an fp32 mean
+    // of a row far from zero (mean 30, std 0.5) is off by up to half an ulp of the mean, which xhat
+    // of the columns near it then carries at full size into dgamma; the shifted mean is small
+    const float pivot = __shfl(xv[0], 0, 64);
     float s = 0.f;
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) s += xv[e];
+    for (int e = 0; e < EPL; ++e) {
+      xv[e] -= pivot;
+      s += xv[e];
+    }
     const float mean = bwd_wave_sum(s) / (float)H;
     float v = 0.f;
 #pragma unroll
@@ -438,7 +445,8 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
   float* lse2 = (float*)(Os + Lp * kAbRow);          // [Lp]  lse * log2e
   float* dv = lse2 + Lp;                             // [Lp]  Dv
   float* kb2 = dv + Lp;                              // [Lp]  key bias (0 / -FLT_MAX)
-  uint32_t* kbits = (uint32_t*)(kb2 + Lp);           // [NB][Lp] keep words (DROP)
+  int* wlive = (int*)(kb2 + Lp);                     // [8]   per wave: one of its keys is live
+  uint32_t* kbits = (uint32_t*)(wlive + 8);          // [NB][Lp] keep words (DROP)
   float* rbs = (float*)(kbits + (DROP ? NB * Lp : 0));   // [2 Lp] relative biases * log2e (RB)
   float* dts = rbs + 2 * Lp;                         // [2 Lp] their gradient (RB)
   float* rbq = dts + 2 * Lp;                         // [4][2 Lp + 4] shifted reversed copies of rbs (RB)
@@ -458,6 +466,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
   // ---- staging: every global load of the work-group (the rows of Q, K, V, dO, O, and the per-row
   // lse, mask and keep words) in flight before the first LDS store -- one latency round, which is
   // exposed whenever one work-group holds the CU (L > 128)
+  bool dead;   // every key of the sequence masked
   {
     constexpr int MAXIT = (Lp * 8 + NT - 1) / NT;
     constexpr int MAXS = (Lp + NT - 1) / NT;                        // per-row values per thread
@@ -502,12 +511,32 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       wd[j] = 0u;
       if (src && i < L * NB) wd[j] = src[i];
     }
+    // A sequence with every key masked (drt.h): the forward gave it the uniform mean of V whatever Q,
+    // K and relbias hold, so here P = 1 / L over zeroed Qs / K images and an all-zero bias table:
+    // kb2 = 0, lse2 = log2 L (the forward's lse, near -FLT_MAX ln 2, is not used), dQ = dK = 0 exactly.
+    // (through its own 32 bytes of the dynamic LDS: the work-group reduction of __syncthreads_or
+    // takes static LDS, which the 160 KiB dynamic limit set on these kernels leaves no room for)
+    int anylive = 0;
+#pragma unroll
+    for (int j = 0; j < MAXS; ++j) anylive |= (tid + j * NT < L && mk[j] != 0) ? 1 : 0;
+    const bool wavelive = __ballot(anylive) != 0ull;
+    if (lane == 0) wlive[wave] = wavelive ? 1 : 0;
+    __syncthreads();
+    int live = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) live |= wlive[w];
+    dead = live == 0;
+    const float dead_lse2 = __log2f((float)L);
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
       const int i = tid + it * NT;
       if (i >= Lp * 8) break;
       const int row = i >> 3, c = i & 7;
       float part = 0.f;
+      if (dead) {
+        q[it] = bf16x8{};
+        k[it] = bf16x8{};
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         q[it][j] = (__bf16)((float)q[it][j] * a.scale);
@@ -526,8 +555,8 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
     for (int j = 0; j < MAXS; ++j) {
       const int i = tid + j * NT;
       if (i < Lp) {
-        kb2[i] = (i >= L || mk[j] == 0) ? -3.402823466e+38f : 0.0f;   // (1 - mask) * finfo.min (finite)
-        lse2[i] = lsev[j] * kLog2e;
+        kb2[i] = (i >= L || (mk[j] == 0 && !dead)) ? -3.402823466e+38f : 0.0f;   // (1 - mask) * finfo.min (finite)
+        lse2[i] = dead ? dead_lse2 : lsev[j] * kLog2e;
       }
     }
     if (DROP) {   // -> [key block][query]; without the forward's words (drop_bits NULL) the same
@@ -555,13 +584,13 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
       for (int i = tid; i < 2 * Lp; i += NT) {
         const int j = i - (Lp - L);                  // table entry k - q + L - 1
-        rbs[i] = (j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+        rbs[i] = (j >= 0 && j < 2 * L - 1 && !dead) ? src[j] * kLog2e : 0.0f;
         dts[i] = 0.0f;
       }
       for (int i = tid; i < 4 * 2 * Lp; i += NT) {   // rbq[c][t] = rbs[2 Lp - 2 - (t + c)]
         const int c = i / (2 * Lp), t = i - c * 2 * Lp;
         const int ii = 2 * Lp - 2 - (t + c), j = ii - (Lp - L);
-        rbq[c * (2 * Lp + 4) + t] = (ii >= 0 && j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+        rbq[c * (2 * Lp + 4) + t] = (ii >= 0 && j >= 0 && j < 2 * L - 1 && !dead) ? src[j] * kLog2e : 0.0f;
       }
     }
   }
@@ -777,7 +806,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
   }
   if (RB) {   // this (sequence, head)'s diagonal sums (complete since the barrier after the phases)
     float* dst = a.dtab + ((int64_t)b * a.heads + hd) * (2 * L - 1);
-    for (int i = tid; i < 2 * L - 1; i += NT) dst[i] = dts[i + Lp - L];
+    for (int i = tid; i < 2 * L - 1; i += NT) dst[i] = dead ? 0.0f : dts[i + Lp - L];   // dead: no relbias read
   }
   if (a.dsum && tid < 192) {   // the blocks' column sums in block order -> dsum[b][3H]
     const int m = tid >> 6, col = tid & 63;
@@ -812,13 +841,24 @@ constexpr int kAblGroup = 128;   // rows per work-group (4 waves x 32)
 // a.dtab[sequence][group][head].
 constexpr int kAblRb = 2 * kAblMaxSeq;
 
+// Work-group-wide "every key of sequence b is masked" (256 threads over the L <= 512 mask entries;
+// one barrier, before any LDS traffic).  Such a sequence runs as attention_bwd_rk_kernel's: P = 1 / L
+// from zeroed Qs / K operands, a zero bias table, key bias 0 and lse = ln L (contract: drt.h).
+__device__ __forceinline__ bool abl_dead_sequence(const AttnBwdArgs& a, int64_t b, int L) {
+  int anylive = a.mask == nullptr;
+  if (a.mask)
+    for (int i = threadIdx.x; i < L; i += 256) anylive |= a.mask[b * a.L + i] != 0;
+  return !__syncthreads_or(anylive);
+}
+
 template <bool RB>
-__device__ __forceinline__ void abl_stage_relbias(const AttnBwdArgs& a, int hd, int L, float* rbs, float* dts) {
+__device__ __forceinline__ void abl_stage_relbias(const AttnBwdArgs& a, int hd, int L, bool dead, float* rbs,
+                                                  float* dts) {
   if (!RB) return;
   const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
   for (int i = threadIdx.x; i < kAblRb; i += 256) {
     const int j = i - (kAblMaxSeq - L);              // table entry k - q + L - 1
-    rbs[i] = (j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+    rbs[i] = (j >= 0 && j < 2 * L - 1 && !dead) ? src[j] * kLog2e : 0.0f;
     dts[i] = 0.0f;
   }
 }
@@ -826,13 +866,13 @@ __device__ __forceinline__ void abl_stage_relbias(const AttnBwdArgs& a, int hd, 
 // attention_bwd_rk_kernel's rbq (one aligned 16-B read per four queries).
 constexpr int kAblRbq = kAblRb + 4;
 template <bool RB>
-__device__ __forceinline__ void abl_stage_relbias_rev(const AttnBwdArgs& a, int hd, int L, float* rbq) {
+__device__ __forceinline__ void abl_stage_relbias_rev(const AttnBwdArgs& a, int hd, int L, bool dead, float* rbq) {
   if (!RB) return;
   const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
   for (int i = threadIdx.x; i < 4 * kAblRb; i += 256) {
     const int c = i / kAblRb, t = i - c * kAblRb;
     const int ii = kAblRb - 2 - (t + c), j = ii - (kAblMaxSeq - L);
-    rbq[c * kAblRbq + t] = (ii >= 0 && j >= 0 && j < 2 * L - 1) ? src[j] * kLog2e : 0.0f;
+    rbq[c * kAblRbq + t] = (ii >= 0 && j >= 0 && j < 2 * L - 1 && !dead) ? src[j] * kLog2e : 0.0f;
   }
 }
 
@@ -866,6 +906,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
   const int key = blk * 32 + r;
   const bool active = blk * 32 < L;                  // wave-uniform
   const int keyc = key < L ? key : L - 1;
+  const bool dead = abl_dead_sequence(a, b, L);      // every key masked: P = 1 / L over zeroed Qs, K
   bf16x8 kf[4], vf[4];                               // B operands of S = Qs K^T, dP = dO V^T
 #pragma unroll
   for (int k4 = 0; k4 < 4; ++k4) {
@@ -875,8 +916,11 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
       kf[k4] = bf16x8{};
       vf[k4] = bf16x8{};
     }
+    if (dead) kf[k4] = bf16x8{};
   }
-  const float kbias = (key >= L || (a.mask && a.mask[b * a.L + key] == 0)) ? -3.402823466e+38f : 0.0f;
+  const float kbias =
+      (key >= L || (!dead && a.mask && a.mask[b * a.L + key] == 0)) ? -3.402823466e+38f : 0.0f;
+  const float dead_lse2 = __log2f((float)L);
   const float inv = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
   const AbOffsets off = ab_offsets(lane);
   const uint32_t lanebit = 1u << r;
@@ -890,7 +934,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
     const int q = qb * 32 + srow;
     gq = go = goo = bf16x8{};
     if (q < L) {
-      gq = *(const bf16x8*)(Qg + (int64_t)q * ld + sc * 8);
+      if (!dead) gq = *(const bf16x8*)(Qg + (int64_t)q * ld + sc * 8);
       go = *(const bf16x8*)(dOg + (int64_t)q * a.H + sc * 8);
       goo = *(const bf16x8*)(Og + (int64_t)q * a.H + sc * 8);
     }
@@ -915,7 +959,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
     part += __shfl_xor(part, 4, 64);
     if (sc == 0) dvs[srow] = part;
     // rows past L: lse2 = +inf makes P = 0 (their dO is 0 too)
-    if (tid < 32) lse2[tid] = qb * 32 + tid < L ? glse * kLog2e : __builtin_inff();
+    if (tid < 32) lse2[tid] = qb * 32 + tid < L ? (dead ? dead_lse2 : glse * kLog2e) : __builtin_inff();
     if (DROP && tid < 128) kw[tid >> 5][tid & 31] = gw;
   };
 
@@ -927,7 +971,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dkdv_kernel(AttnBwd
       dK[t][e] = 0.f;
       dV[t][e] = 0.f;
     }
-  abl_stage_relbias_rev<RB>(a, hd, L, rbq);         // visible after the loop's first barrier
+  abl_stage_relbias_rev<RB>(a, hd, L, dead, rbq);   // visible after the loop's first barrier
   const float* rbq1 = rbq + (RB ? ((kAblMaxSeq - 1 - key) & 3) * kAblRbq + ((kAblMaxSeq - 1 - key) & ~3) : 0);
   load(0);
   for (int qb = 0; qb < nqb; ++qb) {
@@ -1040,6 +1084,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
   const int q = blk * 32 + r;                        // this lane's query (D column)
   const bool active = blk * 32 < L;
   const int qc = q < L ? q : L - 1;
+  const bool dead = abl_dead_sequence(a, b, L);      // every key masked: P = 1 / L over zeroed Qs, K
   bf16x8 qf[4], of[4];                               // B operands of S^T = K Qs^T, dP^T = V dO^T
   float part = 0.f;
 #pragma unroll
@@ -1052,12 +1097,12 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
       x[j] = (__bf16)((float)x[j] * a.scale);
       part += (float)o[j] * (float)oo[j];
     }
-    qf[k4] = q < L ? x : bf16x8{};
+    qf[k4] = q < L && !dead ? x : bf16x8{};
     of[k4] = q < L ? o : bf16x8{};
   }
   part += __shfl_xor(part, 32, 64);                 // Dv over the 64 d (the two lane halves)
   const float dq = part;
-  const float lq = q < L ? a.lse[hrow + q] * kLog2e : __builtin_inff();
+  const float lq = q < L ? (dead ? __log2f((float)L) : a.lse[hrow + q] * kLog2e) : __builtin_inff();
   const float inv = DROP ? 1.0f / (1.0f - a.drop_p) : 1.0f;
   const AbOffsets off = ab_offsets(lane);
 
@@ -1069,12 +1114,12 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
     const int kk = kb * 32 + srow;
     gk = gv = bf16x8{};
     if (kk < L) {
-      gk = *(const bf16x8*)(Kg + (int64_t)kk * ld + sc * 8);
+      if (!dead) gk = *(const bf16x8*)(Kg + (int64_t)kk * ld + sc * 8);
       gv = *(const bf16x8*)(Vg + (int64_t)kk * ld + sc * 8);
     }
     if (tid < 32) {
       const int k2 = kb * 32 + tid;
-      gkb = (k2 >= L || (a.mask && a.mask[b * a.L + k2] == 0)) ? -3.402823466e+38f : 0.0f;
+      gkb = (k2 >= L || (!dead && a.mask && a.mask[b * a.L + k2] == 0)) ? -3.402823466e+38f : 0.0f;
     }
     if (DROP) gw = q < L ? a.drop_bits[(hrow + q) * nkw + kb] : 0u;
   };
@@ -1088,7 +1133,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) dQ[t][e] = 0.f;
-  abl_stage_relbias<RB>(a, hd, L, rbs, dts);        // visible after the loop's first barrier
+  abl_stage_relbias<RB>(a, hd, L, dead, rbs, dts);  // visible after the loop's first barrier
   load(0);
   for (int kb = 0; kb < nkb; ++kb) {
     store();
@@ -1160,7 +1205,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
   if (RB) {   // complete since the loop's last barrier
     const int G = (L + kAblGroup - 1) / kAblGroup;
     float* dst = a.dtab + (((int64_t)b * G + grp) * a.heads + hd) * (2 * L - 1);
-    for (int i = tid; i < 2 * L - 1; i += 256) dst[i] = dts[i + kAblMaxSeq - L];
+    for (int i = tid; i < 2 * L - 1; i += 256) dst[i] = dead ? 0.0f : dts[i + kAblMaxSeq - L];
   }
   if (a.dsum && tid < 64) {
     const int G = (L + kAblGroup - 1) / kAblGroup;
@@ -1377,7 +1422,7 @@ int drt_attention_backward_bf16(const void* qkv, const void* ctx, const void* dc
     const int Lp = ((int)L + 31) & ~31;
     const int nb = Lp / 32;
     // register-resident P / dS; dropout from the forward's keep bits (or the same bits drawn again)
-    const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + (drop ? (size_t)nb * Lp * 4 : 0) +
+    const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + 32 + (drop ? (size_t)nb * Lp * 4 : 0) +
                        (rb ? (size_t)4 * Lp * 4 + (size_t)4 * (2 * Lp + 4) * 4 : 0);   // RB: the bias diagonals and
                                                 // their gradient, 2 Lp floats each, + 4 shifted reversed copies
     DRT_REQUIRE(lds <= 160 * 1024);

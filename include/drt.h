@@ -431,6 +431,13 @@ int drt_layernorm_bf16(const void* X, int64_t M, int32_t H, const float* gamma,
  *   seed, site).  The scores are rebuilt as S = Qs K^T + relbias[h][k - q + L - 1] + key bias.
  *   L <= 160: one work-group per (sequence, head) holding the sequence in LDS; 160 < L <= 512:
  *     streamed dK / dV and dQ kernels over 128-row groups.
+ *   A masked key's dK and dV rows are exact zeros.  A sequence with every key masked gets the
+ *     gradient of what the forward computes for it, the uniform mean of V whatever Q, K and relbias
+ *     hold: its dQ and dK rows are exact zeros, it adds exact zeros to dtable, its
+ *     dV = sum_q keep dO_q / (L (1 - drop_p)); everything is finite (its lse, near -FLT_MAX ln 2, is
+ *     not read), dctx = 0 on it gives all-zero rows, and the other sequences' rows and partial sums
+ *     have the bits they have under any other mask of that sequence.  HF's autograd gives non-zero
+ *     dQ and dK there only because fp32 absorbed the scores into finfo.min; that is not reproduced.
  *   drop_bits: the forward's keep bits, read instead of regenerating the hash twice per (query,
  *     key); NULL = regenerate (same masks, same results).  For L > 160 with drop_p > 0 the
  *     backward requires drop_bits (DRT_EINVAL without).
