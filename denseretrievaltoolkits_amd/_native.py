@@ -147,6 +147,13 @@ _SIGNATURES = [
     ("drt_attention_varlen_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_f32, c_vp]),
     ("drt_pool_packed_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     ("drt_unpack_rows_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    ("drt_attention_varlen_train_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp,
+                                                        c_vp, c_i32, c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
+    ("drt_attention_varlen_backward_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32,
+                                                   c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
+    ("drt_pack_rows_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    ("drt_embed_ln_pre_packed", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
+                                        c_i32, c_vp, c_vp, c_vp]),
     ("drt_t5_embed_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp]),
     ("drt_rmsnorm_bf16", c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
     ("drt_gated_gelu_new_bf16", c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp]),

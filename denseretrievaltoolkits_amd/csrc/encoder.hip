@@ -12,7 +12,8 @@
 //                   operand (no LDS round trip for P); the RB instantiations add T5's
 //                   relative-position bias to the scores (drt_attention_forward_bf16, relbias);
 //                   the VL instantiations read each sequence's rows from a sequence-offset
-//                   table (packed batches, drt_attention_varlen_forward_bf16; csrc/packed.hip)
+//                   table (packed batches, drt_attention_varlen_forward_bf16; csrc/packed.hip), with
+//                   lse and dropout for training (drt_attention_varlen_train_forward_bf16)
 //   pool            first / masked-mean / masked-max pooling (utils.py:233-240)
 //   l2norm          F.normalize(reps, dim=1) (biencoder.py:149-150)
 #include "drt_common.h"
@@ -226,6 +227,10 @@ struct AttnArgs {
   const int32_t* cu_seqlens;  // [B + 1] row offsets of the sequences; B, L, mask, lse and the dropout fields unused
   const int32_t* seq_ids;     // [n_seqs] the sequences this launch covers, or null: 0 .. n_seqs - 1
   int max_len;                // bound of every listed length (the launch's LDS image); longer ones are clamped
+  // VL training forward (drt_attention_varlen_train_forward_bf16): lse is [heads][T], drop_bits [heads][T][W]
+  // (row cu[b] + q of head h), and the keep hash takes the padded batch's row (b * heads + h) * L_pad + q
+  int64_t L_pad, T;
+  int W;
 };
 
 // Attention forward, one work-group per (sequence, head): K (swizzled rows), V^T and the key bias
@@ -259,8 +264,13 @@ constexpr float kLn2 = 0.6931471805599453f;
 // VL (packed inference batches, csrc/packed.hip): the work-group's sequence is seq_ids[blockIdx.x / heads]
 // (or that index itself), its rows start at cu[b] and its length is cu[b + 1] - cu[b], read per
 // work-group; no mask (a packed sequence has no masked keys: kb is 0 below len, -inf in the tile
-// padding), no lse, no dropout.  NB is the launch's length class: every listed len <= 32 NB.
-template <int NB, bool DROP, bool RB = false, bool VL = false>
+// padding).  NB is the launch's length class: every listed len <= 32 NB.  The training form
+// (lse given, DROP) writes lse as [heads][T] and the keep words as [heads][T][W], W = the batch's
+// word count whatever this launch's class is, and hashes the keeps with the PADDED batch's row
+// (b * heads + head) * L_pad + q: for one (p, seed, site) every real (q, key) keeps what the padded
+// forward keeps.
+// VL = 1: the inference form (no lse, no dropout), VL = 2: the training form.
+template <int NB, bool DROP, bool RB = false, int VL = 0>
 __global__ __launch_bounds__(NB == 5 ? 320 : 256) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void attention_fwd_kernel(AttnArgs a) {
   constexpr int NW = NB == 5 ? 5 : 4;
@@ -287,7 +297,9 @@ void attention_fwd_kernel(AttnArgs a) {
   const int wave = tid >> 6, lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
   const int hd = blockIdx.x % a.heads;
-  const int64_t hrow = ((int64_t)b * a.heads + hd) * L;
+  const int64_t hrow = ((int64_t)b * a.heads + hd) * (VL ? a.L_pad : (int64_t)L);   // row of the keep hash
+  const int64_t orow = VL ? (int64_t)hd * a.T + row0 : hrow;                        // row of lse / drop_bits
+  const int bw = VL ? a.W : nqb;                                                    // keep words per query
   const int64_t ld = 3 * (int64_t)a.H;
   const __bf16* Qg = a.qkv + row0 * ld + hd * kHeadDim;
   const __bf16* Kg = Qg + a.H;
@@ -376,6 +388,10 @@ void attention_fwd_kernel(AttnArgs a) {
     const uint32_t rowkey = DROP ? attn_row_key(a.seed, a.site, (uint64_t)(hrow + qq)) : 0u;
     const float* rbq = rb + (L - 1 - qrow);    // RB: this query's bias of key k is rbq[k], k < Lp
     uint32_t words[NB ? NB : 1];               // keep words of this query (stored once, after the last tile)
+    if (VL && DROP) {                          // the tiles a short sequence skips hold no kept key
+#pragma unroll
+      for (int j = 0; j < (NB ? NB : 1); ++j) words[j] = 0u;
+    }
     f32x16 o[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -457,7 +473,7 @@ void attention_fwd_kernel(AttnArgs a) {
         if (a.drop_bits) {   // this query's 32 keep bits of the key tile: the two lane halves' 16 each
           const uint32_t word = m16 | __shfl_xor(m16, 32, 64);
           if (NB) words[NB ? (kt / 32) % NB : 0] = word;
-          else if (h == 0 && qq < L) a.drop_bits[(hrow + qq) * nqb + kt / 32] = word;
+          else if (h == 0 && qq < L) a.drop_bits[(orow + qq) * bw + kt / 32] = word;
         }
       }
       // O^T += V^T P^T over the 32 keys (2 k-steps of 16)
@@ -486,8 +502,8 @@ void attention_fwd_kernel(AttnArgs a) {
       for (int j = 0; j < (NB ? NB : 1); ++j)
         if (!VL || j < nqv) tile(32 * j);
       if (DROP && a.drop_bits && h == 0 && qq < L) {   // the row's words: contiguous over the wave's queries
-        uint32_t* dst = a.drop_bits + (hrow + qq) * nqb;
-        if (NB == 4) {
+        uint32_t* dst = a.drop_bits + (orow + qq) * bw;
+        if (NB == 4 && !VL) {
           *(u32x4*)dst = u32x4{words[0], words[NB > 1 ? 1 : 0], words[NB > 2 ? 2 : 0], words[NB > 3 ? 3 : 0]};
         } else {
 #pragma unroll
@@ -498,7 +514,7 @@ void attention_fwd_kernel(AttnArgs a) {
       for (int kt = 0; kt < Lp; kt += 32) tile(kt);
     }
     // O^T[d][q]: lane holds query r; d = 32t + (e&3) + 8(e>>2) + 4h
-    if (!VL && qq < L && a.lse && h == 0) a.lse[hrow + qq] = (m + __log2f(l)) * kLn2;
+    if (VL != 1 && qq < L && a.lse && h == 0) a.lse[orow + qq] = (m + __log2f(l)) * kLn2;
     const float sc = inv / l;
     if (NB) {
 #pragma unroll
@@ -742,9 +758,9 @@ int drt_attention_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens
              nullptr, nullptr, cu_seqlens, seq_ids, max_len};
   using Kernel = void (*)(AttnArgs);
   static constexpr Kernel kernels[6] = {
-      attention_fwd_kernel<0, false, false, true>, attention_fwd_kernel<1, false, false, true>,
-      attention_fwd_kernel<2, false, false, true>, attention_fwd_kernel<3, false, false, true>,
-      attention_fwd_kernel<4, false, false, true>, attention_fwd_kernel<5, false, false, true>};
+      attention_fwd_kernel<0, false, false, 1>, attention_fwd_kernel<1, false, false, 1>,
+      attention_fwd_kernel<2, false, false, 1>, attention_fwd_kernel<3, false, false, 1>,
+      attention_fwd_kernel<4, false, false, 1>, attention_fwd_kernel<5, false, false, 1>};
   const int Lp = ((int)max_len + 31) & ~31;
   const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
   const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;
@@ -757,6 +773,41 @@ int drt_attention_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens
   void* args[] = {&a};
   hipLaunchKernel((const void*)kernels[nb], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
                   (hipStream_t)stream);
+  return hip_status(hipGetLastError());
+}
+
+// The training forward over a packed batch (contract: drt.h): VL x {plain, DROP} at the five
+// whole-sequence classes -- what the varlen backward (encoder_bwd.hip) can differentiate.  At
+// drop_p = 0 it is the inference entry's arithmetic with lse switched on (its own instantiation, so
+// the inference kernels keep their registers).
+int drt_attention_varlen_train_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                            int64_t n_seqs, int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                            void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
+                                            int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
+                                            void* stream) {
+  constexpr int kMaxTrainLen = 160;
+  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kMaxTrainLen && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
+  if (n_seqs == 0 || T == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && cu_seqlens && ctx && L_pad >= max_len);
+  const bool drop = drop_p > 0.0f;
+  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
+  AttnArgs a{(const __bf16*)qkv, nullptr, (__bf16*)ctx, 0, 0, heads, heads * head_dim, scale, lse, drop_p, seed, site,
+             drop ? drop_bits : nullptr, nullptr, cu_seqlens, seq_ids, max_len, L_pad, T, W};
+  using Kernel = void (*)(AttnArgs);
+  static constexpr Kernel kernels[5][2] = {
+      {attention_fwd_kernel<1, false, false, 2>, attention_fwd_kernel<1, true, false, 2>},
+      {attention_fwd_kernel<2, false, false, 2>, attention_fwd_kernel<2, true, false, 2>},
+      {attention_fwd_kernel<3, false, false, 2>, attention_fwd_kernel<3, true, false, 2>},
+      {attention_fwd_kernel<4, false, false, 2>, attention_fwd_kernel<4, true, false, 2>},
+      {attention_fwd_kernel<5, false, false, 2>, attention_fwd_kernel<5, true, false, 2>}};
+  const int Lp = ((int)max_len + 31) & ~31;
+  const int nb = Lp / 32;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;   // <= 42 KiB
+  void* args[] = {&a};
+  hipLaunchKernel((const void*)kernels[nb - 1][drop], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 320 : 256), args,
+                  lds, (hipStream_t)stream);
   return hip_status(hipGetLastError());
 }
 

@@ -304,6 +304,13 @@ struct AttnBwdArgs {
   const float* relbias;       // RB kernels: [heads][2L-1] fp32, the forward's relative-position bias
   float* dtab;                // RB kernels: [B][heads][2L-1] (L > 160: [B][ceil(L / 128)][heads][2L-1]) fp32,
                               // each work-group's sums of dS along the diagonals k - q
+  // VL kernels (packed batches, drt_attention_varlen_backward_bf16): qkv / ctx / dctx / dqkv hold T token rows,
+  // lse is [heads][T], drop_bits [heads][T][W], dsum [sequences][3H]; B, L and mask unused
+  const int32_t* cu_seqlens;  // [sequences + 1] row offsets
+  const int32_t* seq_ids;     // [n_seqs] the sequences this launch covers, or null: 0 .. n_seqs - 1
+  int max_len;                // bound of every listed length (<= 32 NB); longer ones are clamped
+  int64_t L_pad, T;           // the keep hash's row is (b * heads + head) * L_pad + q (the padded batch's)
+  int W;                      // keep words per query in drop_bits
 };
 
 __device__ __forceinline__ int ab_rc(int row, int chunk) { return row * kAbRow + ((chunk ^ ((row >> 1) & 7)) << 4); }
@@ -431,13 +438,30 @@ __device__ __forceinline__ void ab_p2_pairs(const f32x16& st, const f32x16& dpt,
 // queries and keys add nothing.  The work-group's 2L-1 sums go to a.dtab[sequence][head]; the host
 // sums the sequences in a fixed order.  (The LDS atomics of the query blocks of one work-group land
 // in hardware order: dtable is deterministic across sequences, not bit-reproducible within one.)
-template <int NB, bool DROP, bool RB = false>
+// VL (packed batches): the work-group's sequence is seq_ids[blockIdx.x / heads] (or that index itself),
+// its rows start at cu[b], its length is cu[b + 1] - cu[b] clamped to max_len; NB is the launch's length
+// class.  No mask, so no dead path.  lse is [heads][T], the keep words [heads][T][W], the hash row the
+// padded batch's (the varlen training forward, encoder.hip).  A sequence shorter than the class skips
+// the row blocks that hold no token by work-group-uniform branches: a padding query adds exact zeros
+// to dK / dV (its dO row and Dv are 0), a padding key exact zeros to dQ (P = 0), so the bits are those
+// of the run at the sequence's own class.
+template <int NB, bool DROP, bool RB = false, bool VL = false>
 __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void attention_bwd_rk_kernel(AttnBwdArgs a) {
   constexpr int NW = NB == 5 ? 8 : 4;
   constexpr int NT = NW * 64;
   constexpr int Lp = NB * 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int L = (int)a.L;
+  const int64_t b = VL ? (a.seq_ids ? a.seq_ids[blockIdx.x / a.heads] : blockIdx.x / a.heads) : blockIdx.x / a.heads;
+  const int64_t row0 = VL ? a.cu_seqlens[b] : b * a.L;
+  int Lv = 0;
+  if (VL) {   // clamped to the launch's bound: a wrong table cannot run past the LDS image
+    Lv = a.cu_seqlens[b + 1] - (int)row0;
+    Lv = Lv < a.max_len ? Lv : a.max_len;
+    Lv = Lv < Lp ? Lv : Lp;
+    if (Lv <= 0) return;                    // the whole work-group: no barrier is left waiting
+  }
+  const int L = VL ? Lv : (int)a.L;
+  const int nbv = VL ? (L + 31) >> 5 : NB;  // row blocks that hold a token
   char* Qs = smem;                                   // [Lp][64] (scaled Q)
   char* Ks = Qs + Lp * kAbRow;
   char* Vs = Ks + Lp * kAbRow;
@@ -453,9 +477,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
-  const int64_t b = blockIdx.x / a.heads;
   const int hd = blockIdx.x % a.heads;
-  const int64_t row0 = b * a.L;
   const int64_t ld = 3 * (int64_t)a.H;
   const __bf16* Qg = a.qkv + row0 * ld + hd * 64;
   const __bf16* Kg = Qg + a.H;
@@ -471,7 +493,8 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
     constexpr int MAXIT = (Lp * 8 + NT - 1) / NT;
     constexpr int MAXS = (Lp + NT - 1) / NT;                        // per-row values per thread
     constexpr int MAXW = DROP ? (NB * Lp + NT - 1) / NT : 1;        // keep words
-    const int64_t hrow = ((int64_t)b * a.heads + hd) * a.L;
+    const int64_t hrow = ((int64_t)b * a.heads + hd) * (VL ? a.L_pad : a.L);   // row of the keep hash
+    const int64_t orow = VL ? (int64_t)hd * a.T + row0 : hrow;                  // row of lse / drop_bits
     bf16x8 q[MAXIT], k[MAXIT], v[MAXIT], o[MAXIT], oo[MAXIT];
     float lsev[MAXS];
     int64_t mk[MAXS];
@@ -499,33 +522,38 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       lsev[j] = 0.0f;
       mk[j] = 1;
       if (i < L) {
-        lsev[j] = a.lse[hrow + i];
-        if (a.mask) mk[j] = a.mask[b * a.L + i];
+        lsev[j] = a.lse[orow + i];
+        if (!VL && a.mask) mk[j] = a.mask[b * a.L + i];
       }
     }
     // [query][key block] words of the forward, read in their own order (coalesced)
-    const uint32_t* src = DROP && a.drop_bits ? a.drop_bits + hrow * NB : nullptr;
+    // (VL: W words per query, of which this class reads the first NB)
+    const uint32_t* src = DROP && a.drop_bits ? a.drop_bits + orow * (VL ? a.W : NB) : nullptr;
 #pragma unroll
     for (int j = 0; j < MAXW; ++j) {
       const int i = tid + j * NT;
       wd[j] = 0u;
-      if (src && i < L * NB) wd[j] = src[i];
+      if (src && i < L * NB) wd[j] = VL ? src[(i / NB) * a.W + i % NB] : src[i];
     }
     // A sequence with every key masked (drt.h): the forward gave it the uniform mean of V whatever Q,
     // K and relbias hold, so here P = 1 / L over zeroed Qs / K images and an all-zero bias table:
     // kb2 = 0, lse2 = log2 L (the forward's lse, near -FLT_MAX ln 2, is not used), dQ = dK = 0 exactly.
     // (through its own 32 bytes of the dynamic LDS: the work-group reduction of __syncthreads_or
     // takes static LDS, which the 160 KiB dynamic limit set on these kernels leaves no room for)
-    int anylive = 0;
+    if (VL) {
+      dead = false;   // no mask
+    } else {
+      int anylive = 0;
 #pragma unroll
-    for (int j = 0; j < MAXS; ++j) anylive |= (tid + j * NT < L && mk[j] != 0) ? 1 : 0;
-    const bool wavelive = __ballot(anylive) != 0ull;
-    if (lane == 0) wlive[wave] = wavelive ? 1 : 0;
-    __syncthreads();
-    int live = 0;
+      for (int j = 0; j < MAXS; ++j) anylive |= (tid + j * NT < L && mk[j] != 0) ? 1 : 0;
+      const bool wavelive = __ballot(anylive) != 0ull;
+      if (lane == 0) wlive[wave] = wavelive ? 1 : 0;
+      __syncthreads();
+      int live = 0;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) live |= wlive[w];
-    dead = live == 0;
+      for (int w = 0; w < NW; ++w) live |= wlive[w];
+      dead = live == 0;
+    }
     const float dead_lse2 = __log2f((float)L);
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
@@ -621,7 +649,15 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
   bf16x8 dKo[2][2], dVo[2][2], dQo[2][2];             // [t][e >> 3]: element e of column 32 t + r
 
   // ---- P1: dK, dV of key block p1
-  if (p1 >= 0) {
+  if (VL && p1 >= nbv) {   // a key block without a token: zeros for the image and the column sums
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        dKo[t][g] = bf16x8{};
+        dVo[t][g] = bf16x8{};
+      }
+  } else if (p1 >= 0) {
     const int blk = p1;
     const int key = blk * 32 + r;                     // this lane's key (D column / A row)
     bf16x8 kf[4], vf[4];                              // B operands of S = Qs K^T, dP = dO V^T
@@ -642,6 +678,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       }
 #pragma unroll
     for (int qb = 0; qb < NB; ++qb) {
+      if (VL && qb >= nbv) break;   // query blocks without a token add exact zeros
       f32x16 sv, dp;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
@@ -692,7 +729,12 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
   }
 
   // ---- P2: dQ of query block p2
-  if (p2 >= 0) {
+  if (VL && p2 >= nbv) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 2; ++g) dQo[t][g] = bf16x8{};
+  } else if (p2 >= 0) {
     const int blk = p2;
     const int q = blk * 32 + r;                        // this lane's query (D column)
     bf16x8 qf[4], of[4];                               // B operands of S^T = K Qs^T, dP^T = V dO^T
@@ -709,6 +751,7 @@ __global__ __launch_bounds__((NB == 5 ? 8 : 4) * 64, NB == 5 ? 1 : 2) void atten
       for (int e = 0; e < 16; ++e) dQ[t][e] = 0.f;
 #pragma unroll
     for (int kbk = 0; kbk < NB; ++kbk) {
+      if (VL && kbk >= nbv) break;   // key blocks without a token: P = 0
       f32x16 st, dpt;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
@@ -1446,6 +1489,46 @@ int drt_attention_backward_bf16(const void* qkv, const void* ctx, const void* dc
   }
   const int64_t n = (int64_t)heads * (2 * L - 1);
   return colsum_launch<float>(part, rows, n, dtable, part + (size_t)rows * n, st);
+}
+
+// The attention backward over a packed batch (contract: drt.h): the VL instantiations of the
+// whole-sequence kernel, one work-group per (listed sequence, head); max_len picks the class and
+// sizes the LDS image.  dsum rows are per sequence, so the launches of one batch (one per length
+// class, or one for all) fill one [B][3H] matrix that the caller sums once.
+int drt_attention_varlen_backward_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                       const int32_t* cu_seqlens, const int32_t* seq_ids, int64_t n_seqs,
+                                       int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                       const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads,
+                                       int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
+                                       void* stream) {
+  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kAbMaxSeq && heads > 0 && head_dim == 64);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
+  if (n_seqs == 0 || T == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx && dctx && lse && cu_seqlens && dqkv && L_pad >= max_len);
+  const bool drop = drop_p > 0.0f;
+  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
+  AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, nullptr, (__bf16*)dqkv, 0, 0,
+                heads, heads * 64, scale, drop_p, seed, site, drop ? drop_bits : nullptr, dsum, nullptr, nullptr,
+                cu_seqlens, seq_ids, max_len, L_pad, T, W};
+  using Kernel = void (*)(AttnBwdArgs);
+#define DRT_AB_VL(NB) {attention_bwd_rk_kernel<NB, false, false, true>, attention_bwd_rk_kernel<NB, true, false, true>}
+  static constexpr Kernel vl[5][2] = {DRT_AB_VL(1), DRT_AB_VL(2), DRT_AB_VL(3), DRT_AB_VL(4), DRT_AB_VL(5)};
+#undef DRT_AB_VL
+  const int Lp = ((int)max_len + 31) & ~31;
+  const int nb = Lp / 32;
+  const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + 32 + (drop ? (size_t)nb * Lp * 4 : 0);
+  static bool vl_attr = false;
+  if (!vl_attr) {   // NB = 5 stages more than the default 64 KiB
+    for (const auto& by_drop : vl)
+      for (const Kernel k : by_drop)
+        DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    vl_attr = true;
+  }
+  void* args[] = {&a};
+  hipLaunchKernel((const void*)vl[nb - 1][drop], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 512 : 256), args, lds,
+                  (hipStream_t)stream);
+  return hip_status(hipGetLastError());
 }
 
 // The earlier names (drt.h, "Earlier attention names"): argument subsets of the two entries above.

@@ -18,7 +18,11 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   returns differentiable reps) runs BERT towers up to L = 512 on the HIP training
   tower (model/train_tower.py: forward with saved bf16 activations + backward on
   HIP kernels, HF train-mode dropout regenerated from a counter hash; dropout is
-  off in eval mode).  ``encoder_only`` T5 towers stay on the HF module under
+  off in eval mode).  With ``hip_packed_train = True`` (attribute, or
+  ``model_args.hip_packed_train``; default off, separate from ``hip_packed``) that tower
+  runs on the packed real tokens of the batch (sequences up to 160 tokens, a padding share
+  of at least ``packing.hip_packed_train_min_saving``; otherwise padded, logged once).
+  ``encoder_only`` T5 towers stay on the HF module under
   autograd by default; with ``hip_train_t5 = True`` (attribute, or
   ``model_args.hip_train_t5``) a supported T5EncoderModel on the GPU runs the HIP
   T5 training tower (model/t5_train_tower.py: RMSNorm / ReLU / gated-GELU /
@@ -46,6 +50,7 @@ from transformers import AutoModel, BatchEncoding, PreTrainedModel
 from transformers.modeling_outputs import ModelOutput
 
 from .encoder import HipBertEncoder, l2_normalize_, linear_head
+from . import packing
 from .packing import plan_packing
 from .t5_encoder import HipT5Encoder, t5_supported
 from .train_tower import MAX_TRAIN_SEQ, tower_supported, train_hidden
@@ -90,6 +95,20 @@ def packed_plan(enc, items):
     return plan
 
 
+def packed_train_plan(items, dev):
+    """The packing plan of a batch for a training pass with ``hip_packed_train`` set, or None (padded
+    tower, the reason logged once): the mask is not a batch of non-empty prefixes, or its padding
+    share is below ``packing.hip_packed_train_min_saving``."""
+    ids = items["input_ids"]
+    plan = plan_packing(items.get("attention_mask"), ids.shape[1], device=dev,
+                        min_saving=packing.hip_packed_train_min_saving)
+    if plan is None or plan.B != ids.shape[0]:
+        _log_fallback("hip_packed_train: padded tower, the mask is not a batch of non-empty prefixes with "
+                      "enough padding to drop")
+        return None
+    return plan
+
+
 def _torch_mean_pooling(h, mask):
     m = mask.unsqueeze(-1).expand(h.size()).float()
     return torch.sum(h * m, 1) / torch.clamp(m.sum(1), min=1e-9)
@@ -120,6 +139,9 @@ class DRModel(nn.Module):
         # opt-in: padding-free inference of BERT towers (only the real tokens of a padded batch are
         # computed; model/packing.py, HipBertEncoder.forward_packed)
         self.hip_packed = bool(getattr(model_args, "hip_packed", False))
+        # opt-in: padding-free TRAINING of BERT towers (the autograd pass of train_hidden on the packed
+        # rows; model/train_tower.py).  Separate from hip_packed, which covers the no-grad encode only.
+        self.hip_packed_train = bool(getattr(model_args, "hip_packed_train", False))
         self.normalize = normalize
         self.model_args = model_args
         self.train_args = train_args
@@ -274,11 +296,14 @@ class DRModel(nn.Module):
             why = f"sequence length {items['input_ids'].shape[1]} > {MAX_TRAIN_SEQ}"
         else:
             why = tower_supported(model)
+        if self.hip_packed_train and (why is not None or is_t5):
+            _log_fallback("hip_packed_train: no packed tower, " + (why or "a T5 tower has no packed form"))
         if why is None and is_t5:
             hidden = train_hidden_t5(model, items["input_ids"], items.get("attention_mask"))
         elif why is None:
+            plan = packed_train_plan(items, next(model.parameters()).device) if self.hip_packed_train else None
             hidden = train_hidden(model, items["input_ids"], items.get("attention_mask"),
-                                  token_type_ids=items.get("token_type_ids"))
+                                  token_type_ids=items.get("token_type_ids"), plan=plan)
         else:
             _log_fallback(why)
             out = model(**items, return_dict=True)

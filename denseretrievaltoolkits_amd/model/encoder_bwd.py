@@ -116,6 +116,85 @@ def attention_backward(qkv, ctx, dctx, lse, mask, bits, B, L, heads, scale, relb
     return dqkv, extra
 
 
+def varlen_launches(plan, per_class: bool):
+    """The (seq_ids pointer or None, n_seqs, max_len) of each attention launch over a packed batch: one
+    per length class of the plan, or one for the whole batch."""
+    launches = plan.classes() if per_class else [(None, plan.B, plan.max_len)]
+    return [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]
+
+
+def attention_varlen_forward(qkv, plan, heads, scale, drop=None, per_class=False):
+    """(ctx bf16 [rows, heads*64], lse fp32 [heads, T], keep bits [heads, T, W] or None) of the attention
+    over the packed ``qkv`` [rows >= T, 3 heads*64] of ``plan`` (model/packing.py); rows past T of ctx
+    are zeros.  ``drop`` = (p, seed, site): the keeps of every real (query, key) are those of
+    ``attention_forward`` on the padded batch [B, plan.L]."""
+    dev = qkv.device
+    lib = _native.load()
+    rows, T = qkv.shape[0], plan.T
+    ctx = torch.empty((rows, heads * 64), dtype=torch.bfloat16, device=dev)
+    if rows > T:
+        ctx[T:].zero_()
+    lse = torch.empty((heads, T), dtype=torch.float32, device=dev)
+    p, seed, site = drop if drop is not None else (0.0, 0, 0)
+    W = (plan.max_len + 31) // 32
+    bits = torch.empty((heads, T, W), dtype=torch.int32, device=dev) if p > 0 else None
+    s = _native.stream_ptr(dev)
+    for sp, n, ml in varlen_launches(plan, per_class):
+        _native.check(lib.drt_attention_varlen_train_forward_bf16(
+            qkv.data_ptr(), plan.cu_seqlens.data_ptr(), sp, n, ml, plan.L, T, W, ctx.data_ptr(), lse.data_ptr(),
+            _ptr(bits), heads, 64, float(scale), float(p), seed, site, s), "drt_attention_varlen_train_forward_bf16")
+    return ctx, lse, bits
+
+
+def attention_varlen_backward(qkv, ctx, dctx, lse, bits, plan, heads, scale, drop=None, per_class=False):
+    """(dqkv bf16 like qkv with zero rows past T, dbias fp32 [3 * heads * 64]) of
+    ``attention_varlen_forward``.  Every launch leaves its sequences' column sums in one [B, 3H]
+    matrix; one fixed-order column sum after the last launch finishes dbias."""
+    lib = _native.load()
+    dev = qkv.device
+    rows, T = qkv.shape[0], plan.T
+    dqkv = torch.empty_like(qkv)
+    if rows > T:
+        dqkv[T:].zero_()
+    n3 = 3 * heads * 64
+    dsum = torch.zeros((plan.B, n3), dtype=torch.float32, device=dev)
+    p, seed, site = drop if drop is not None else (0.0, 0, 0)
+    W = (plan.max_len + 31) // 32
+    s = _native.stream_ptr(dev)
+    for sp, n, ml in varlen_launches(plan, per_class):
+        _native.check(lib.drt_attention_varlen_backward_bf16(
+            qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), plan.cu_seqlens.data_ptr(), sp, n, ml,
+            plan.L, T, W, _ptr(bits), dqkv.data_ptr(), dsum.data_ptr(), heads, 64, float(scale), float(p), seed, site,
+            s), "drt_attention_varlen_backward_bf16")
+    dbias = torch.empty(n3, dtype=torch.float32, device=dev)
+    nb = int(lib.drt_colsum_workspace(plan.B, n3))
+    ws = _ws(nb, dev)
+    _native.check(lib.drt_colsum_f32(dsum.data_ptr(), plan.B, n3, dbias.data_ptr(), _ptr(ws), nb, s), "drt_colsum_f32")
+    return dqkv, dbias
+
+
+def pack_rows(padded, plan, rows=None):
+    """[rows, H] bf16 (rows >= T, default T): the real rows of ``padded`` [B * L, H] in packed order,
+    zeros past T -- the inverse of ``unpack_rows`` and its backward."""
+    H = padded.shape[-1]
+    rows = plan.T if rows is None else rows
+    out = torch.empty((rows, H), dtype=torch.bfloat16, device=padded.device)
+    _native.check(_native.load().drt_pack_rows_bf16(padded.data_ptr(), plan.cu_seqlens.data_ptr(), plan.B, plan.L, H,
+                                                    out.data_ptr(), rows, _native.stream_ptr(padded.device)),
+                  "drt_pack_rows_bf16")
+    return out
+
+
+def unpack_rows(packed, plan):
+    """[B * L, H] bf16 from the packed rows [>= T, H]: zeros at the pad positions."""
+    H = packed.shape[-1]
+    out = torch.empty((plan.B * plan.L, H), dtype=torch.bfloat16, device=packed.device)
+    _native.check(_native.load().drt_unpack_rows_bf16(packed.data_ptr(), plan.cu_seqlens.data_ptr(), plan.B, plan.L, H,
+                                                      out.data_ptr(), _native.stream_ptr(packed.device)),
+                  "drt_unpack_rows_bf16")
+    return out
+
+
 def grads_out(names, grads):
     """The autograd nodes' return for the parameters ``names``: fp32 gradients, None where absent."""
     return tuple(grads[n].to(torch.float32) if n in grads else None for n in names)

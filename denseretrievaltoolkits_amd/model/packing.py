@@ -21,6 +21,16 @@ import torch
 # of 0.04; 0.10 leaves that margin.  DESIGN.md §4 "Padding-free inference".
 hip_packed_min_saving = 0.10
 
+# The same threshold for the packed TRAINING tower (DRModel.hip_packed_train; model/train_tower.py).
+# Measured on BERT-base, forward + backward of one tower with dropout (tools/packed_train_ab.py,
+# profiles/packed_train01/packed_train_ab.json): packed / padded time is 0.60 at a padding share of
+# 0.60, 0.76 at 0.37, 0.86 at 0.31 (256 x 160, the smallest GEMMs) and 1.05 with no padding at all and
+# the plan forced (the plan's device-to-host copy drains the launch queue once per step).  The line
+# from the control through the least favourable shape (256 x 160) crosses 1.0 at a share of 0.08, the
+# other two near 0.06; with the margin of 0.06 that the inference threshold got over its crossing,
+# rounded up: 0.15.  DESIGN.md §5 "Padding-free training".
+hip_packed_train_min_saving = 0.15
+
 # Attention length classes: ceil(len / 32) = 1 .. 5 run the kernels that hold the sequence's key
 # blocks in registers, class 0 (len > 160) the streamed form.
 _CLASS_MAX_BLOCKS = 5

@@ -77,6 +77,8 @@ class RRModel(nn.Module):
         self._hip = None
         # opt-in: padding-free inference of a BERT pair tower (model/packing.py); T5 rerankers stay padded
         self.hip_packed = bool(getattr(model_args, "hip_packed", False))
+        # opt-in: padding-free training of a BERT pair tower (model/train_tower.py); separate from hip_packed
+        self.hip_packed_train = bool(getattr(model_args, "hip_packed_train", False))
         if train_args is not None:
             self.loss_fn_str = train_args.loss_fn
             self.margin = train_args.margin
@@ -142,6 +144,9 @@ class RRModel(nn.Module):
             if self.hip_packed:
                 from .biencoder import _log_fallback
                 _log_fallback("hip_packed: padded path, a T5 reranker has no packed form")
+            if self.hip_packed_train and torch.is_grad_enabled():
+                from .biencoder import _log_fallback
+                _log_fallback("hip_packed_train: no packed tower, a T5 reranker has no packed form")
             return self._encode_t5(items)
         if self.pooling not in ("first", "mean"):
             raise ValueError("Unknown pooling type: {}".format(self.pooling))
@@ -166,12 +171,18 @@ class RRModel(nn.Module):
         if (dev.type == "cuda" and self.feature == "last_hidden_state"
                 and tower_supported(self.lm) is None and items["input_ids"].shape[1] <= MAX_TRAIN_SEQ):
             # pair forward + backward on the HIP training tower (model/train_tower.py)
+            plan = None
+            if self.hip_packed_train:
+                from .biencoder import packed_train_plan
+                plan = packed_train_plan(items, dev)
             hidden = train_hidden(self.lm, items["input_ids"], items.get("attention_mask"),
-                                  token_type_ids=items.get("token_type_ids"))
+                                  token_type_ids=items.get("token_type_ids"), plan=plan)
         else:
             from .biencoder import _log_fallback
-            _log_fallback("reranker: " + ("tower on the CPU" if dev.type != "cuda" else
-                                          tower_supported(self.lm) or "feature / length"))
+            why = "tower on the CPU" if dev.type != "cuda" else tower_supported(self.lm) or "feature / length"
+            if self.hip_packed_train:
+                _log_fallback("hip_packed_train: no packed tower, " + why)
+            _log_fallback("reranker: " + why)
             out = self.lm(**items, return_dict=True)
             hidden = getattr(out, self.feature)
         if self.pooling == "first":

@@ -22,6 +22,22 @@ masks are not HF's Philox stream: same distribution and semantics, different dra
 Scope: L <= 512 (BERT max_position_embeddings; L <= 160 -- the recipe, p_max_len 156 -- runs the whole-sequence
 attention backward, longer sequences the streamed one), erf GELU, head_dim 64; anything else
 raises.
+
+Padding-free training (``train_hidden(..., plan=PackingPlan)``, opt-in through
+``DRModel.hip_packed_train`` / ``RRModel.hip_packed_train``): the same nodes run on the packed rows of
+the batch (model/packing.py) instead of the ``[B, L]`` rectangle -- the packed embedding, the varlen
+attention pair (``drt_attention_varlen_train_forward_bf16`` / ``..._backward_bf16``) and, as a last node,
+the unpack to ``[B, L, H]`` with zeros at the pads, whose backward is ``pack_rows``.  Every matrix has
+``T32 = ceil(T / 32) * 32`` rows, so the weight gradients stay on the TN GEMM (which needs a multiple
+of 32 rows).  INVARIANT: the ``T32 - T`` tail rows of every gradient that enters a wgrad or a column
+sum are exactly zero, and the tail rows of every saved activation are finite.  It holds by
+construction: the embedding output, ctx and dqkv are allocated with a zero tail (the attention kernels
+never touch it), ``pack_rows`` zeroes the tail of the incoming gradient, and the LayerNorm, GELU,
+dropout and dgrad of a zero gradient row are zero.  Hidden-site dropout uses the existing kernels and
+GEMM epilogues unchanged, so element (t, j) of a packed matrix draws index ``t * H + j``: the same
+distribution as the padded run, different draws; the attention keeps of every real (query, key) ARE
+the padded run's (the hash takes the padded row).  A plan with ``max_len > 160`` (the streamed
+backward has no varlen form) keeps the padded tower, logged once.
 """
 from __future__ import annotations
 
@@ -31,10 +47,19 @@ import torch
 
 from .. import _native
 from .encoder import BertShape, _check_supported
-from .encoder_bwd import (LIN_GELU, _ptr, attention_backward, attention_forward, dropout, grads_out,
-                          layernorm_backward, linear, linear_backward, transpose_bf16)
+from .encoder_bwd import (LIN_GELU, _ptr, attention_backward, attention_forward, attention_varlen_backward,
+                          attention_varlen_forward, dropout, grads_out, layernorm_backward, linear, linear_backward,
+                          pack_rows, transpose_bf16, unpack_rows)
 
 MAX_TRAIN_SEQ = 512
+MAX_PACKED_TRAIN_LEN = 160   # the whole-sequence attention backward; the streamed one has no varlen form
+
+# Attention launches of the packed tower: False = one launch per batch (forward and backward), True =
+# one per length class of the plan (PackingPlan.classes()).  A/B switch: one launch won in the attention
+# backward alone (one layer at 512 x 128 with lengths 32-128: 182 us in one launch, 205 us in 4, 238 us
+# padded; at 256 x 160: 178 / 186 / 215) and end to end (31.56 against 31.84 ms, 25.06 against 25.29 ms);
+# DESIGN.md §5 "Padding-free training" (tools/packed_train_ab.py, profiles/packed_train01/).
+packed_train_classes = False
 
 
 def tower_supported(model) -> Optional[str]:
@@ -104,11 +129,13 @@ def dropout_sites(layer: int):
 class _Step:
     """What every node of one tower pass shares: weights, shape, masks' inputs, dropout."""
 
-    def __init__(self, model, W: _Weights, ids, mask, drop, types=None):
+    def __init__(self, model, W: _Weights, ids, mask, drop, types=None, plan=None):
         cfg = model.config
         self.model, self.W, self.ids, self.mask, self.drop = model, W, ids, mask, drop
         self.types = types   # token_type_ids [B, L] int64 or None (all type 0)
         self.B, self.L = ids.shape
+        self.plan = plan     # PackingPlan: the tower runs on ``rows`` packed rows, of which plan.T are tokens
+        self.rows = (plan.T + 31) // 32 * 32 if plan is not None else self.B * self.L
         self.H, self.heads, self.eps = cfg.hidden_size, cfg.num_attention_heads, float(cfg.layer_norm_eps)
         self.scale = 1.0 / (self.H // self.heads) ** 0.5
         self.dev = ids.device
@@ -119,13 +146,23 @@ def embed_forward(st: _Step):
     lib = _native.load()
     s = _native.stream_ptr(st.dev)
     W = st.W
-    T = st.B * st.L
+    T = st.rows
     h = torch.empty((T, st.H), dtype=torch.bfloat16, device=st.dev)
     emb_pre = torch.empty_like(h)
-    _native.check(lib.drt_embed_ln_pre(st.ids.data_ptr(), _ptr(st.types), st.B, st.L, W.word.data_ptr(),
-                                       W.pos.data_ptr(),
-                                       W.type.data_ptr(), W.emb_g.data_ptr(), W.emb_b.data_ptr(), st.eps, st.H,
-                                       h.data_ptr(), emb_pre.data_ptr(), s), "drt_embed_ln_pre")
+    if st.plan is not None:
+        pl = st.plan
+        if T > pl.T:   # the tail rows: zeros
+            h[pl.T:].zero_()
+            emb_pre[pl.T:].zero_()
+        _native.check(lib.drt_embed_ln_pre_packed(st.ids.data_ptr(), _ptr(st.types), pl.cu_seqlens.data_ptr(), st.B,
+                                                  st.L, pl.T, W.word.data_ptr(), W.pos.data_ptr(), W.type.data_ptr(),
+                                                  W.emb_g.data_ptr(), W.emb_b.data_ptr(), st.eps, st.H, h.data_ptr(),
+                                                  emb_pre.data_ptr(), s), "drt_embed_ln_pre_packed")
+    else:
+        _native.check(lib.drt_embed_ln_pre(st.ids.data_ptr(), _ptr(st.types), st.B, st.L, W.word.data_ptr(),
+                                           W.pos.data_ptr(),
+                                           W.type.data_ptr(), W.emb_g.data_ptr(), W.emb_b.data_ptr(), st.eps, st.H,
+                                           h.data_ptr(), emb_pre.data_ptr(), s), "drt_embed_ln_pre")
     ph, _, seed = st.drop
     if ph > 0:
         h = dropout(h, ph, seed, 0)
@@ -140,6 +177,9 @@ def embed_backward(st: _Step, emb_pre, d) -> Dict[str, torch.Tensor]:
     if ph > 0:
         d = dropout(d, ph, seed, 0)
     demb, dge, dbe = layernorm_backward(d, emb_pre, W.emb_g, st.eps)
+    if st.plan is not None:
+        # back to the zero-padded rectangle for the scatter-add: zero rows add exact zeros, once per step
+        demb = unpack_rows(demb, st.plan)
     dword = torch.zeros_like(W.word)
     dpos = torch.zeros_like(W.pos)
     dtype = torch.zeros_like(W.type)
@@ -159,11 +199,15 @@ def layer_forward(st: _Step, i: int, h):
     s = _native.stream_ptr(dev)
     ly = st.W.layers[i]
     B, L, H, heads = st.B, st.L, st.H, st.heads
-    T = B * L
+    T = st.rows
     ph, pa, seed = st.drop
     s_att, s_out1, s_out2 = dropout_sites(i)
     qkv = linear(h, ly["wqkv"], torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev), bias=ly["bqkv"])
-    ctx, lse, bits = attention_forward(qkv, st.mask, B, L, heads, st.scale, drop=(pa, seed, s_att))
+    if st.plan is not None:
+        ctx, lse, bits = attention_varlen_forward(qkv, st.plan, heads, st.scale, drop=(pa, seed, s_att),
+                                                  per_class=packed_train_classes)
+    else:
+        ctx, lse, bits = attention_forward(qkv, st.mask, B, L, heads, st.scale, drop=(pa, seed, s_att))
     # x1 = dropout(ctx Wo^T + bo) + h, dropout in the GEMM epilogue
     x1 = linear(ctx, ly["wo"], torch.empty_like(h), bias=ly["bo"], resid=h, drop=(ph, seed, s_out1) if ph > 0 else None)
     h1 = _layernorm(lib, x1, ly["g1"], ly["b1"], st.eps, s)
@@ -204,8 +248,12 @@ def layer_backward(st: _Step, i: int, saved, d) -> Tuple[torch.Tensor, Dict[str,
     dctx, dwo, dbo = linear_backward(dy1, ctx, ly["wo_t"], db=sum1)
     # the attention backward also leaves per-sequence column sums of dQKV: the q / k / v bias
     # gradients without a pass over dQKV
-    dqkv, dbqkv = attention_backward(qkv, ctx, dctx, lse, st.mask, bits, st.B, st.L, heads, st.scale,
-                                     drop=(pa, seed, s_att), want_dbias=True)
+    if st.plan is not None:
+        dqkv, dbqkv = attention_varlen_backward(qkv, ctx, dctx, lse, bits, st.plan, heads, st.scale,
+                                                drop=(pa, seed, s_att), per_class=packed_train_classes)
+    else:
+        dqkv, dbqkv = attention_backward(qkv, ctx, dctx, lse, st.mask, bits, st.B, st.L, heads, st.scale,
+                                         drop=(pa, seed, s_att), want_dbias=True)
     d_in, dwqkv, dbqkv = linear_backward(dqkv, h, ly["wqkv_t"], resid=dx1, db=dbqkv)
     grads = {}
     grads[p + "output.LayerNorm.weight"], grads[p + "output.LayerNorm.bias"] = dg2, db2
@@ -254,6 +302,25 @@ class _LayerFn(torch.autograd.Function):
         return (d_in, None, None, None) + grads_out(ctx.names, grads)
 
 
+class _UnpackFn(torch.autograd.Function):
+    """Last node of the packed tower: [T32, H] packed rows -> [B * L, H] with zeros at the pads; the
+    backward packs the gradient's real rows and zeroes the tail."""
+
+    @staticmethod
+    def forward(ctx, h, st):
+        ctx.st = st
+        return unpack_rows(h, st.plan)
+
+    @staticmethod
+    def backward(ctx, d):
+        return pack_rows(d.contiguous(), ctx.st.plan, ctx.st.rows), None
+
+
+def _log_fallback(why: str):
+    from .biencoder import _log_fallback as log
+    log(why)
+
+
 def _param_groups(model):
     """(embedding names/params, [per-layer names/params]) in the HF naming."""
     named = dict(model.named_parameters())
@@ -266,13 +333,23 @@ def _param_groups(model):
 
 
 def train_hidden(model, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                 seed: Optional[int] = None, token_type_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 seed: Optional[int] = None, token_type_ids: Optional[torch.Tensor] = None, plan=None) -> torch.Tensor:
     """last_hidden_state fp32 [B, L, H] of ``model`` with the HIP tower backward attached (one autograd
     node per layer).  Dropout follows ``model.training`` and the config's probabilities (seed: torch
-    CPU RNG)."""
+    CPU RNG).  ``plan`` (model/packing.py PackingPlan of this batch's mask): the tower runs on the
+    packed rows and the pad positions of the result are zeros; a plan the packed tower cannot take
+    (its longest sequence over 160 tokens, or a plan of another batch shape) keeps the padded tower,
+    logged once."""
     why = tower_supported(model)
     if why is not None:
         raise NotImplementedError(f"HIP training tower: {why}")
+    if plan is not None:
+        if plan.max_len > MAX_PACKED_TRAIN_LEN:
+            _log_fallback(f"hip_packed_train: padded tower, longest sequence {plan.max_len} > {MAX_PACKED_TRAIN_LEN}")
+            plan = None
+        elif (plan.B, plan.L) != tuple(input_ids.shape):
+            _log_fallback("hip_packed_train: padded tower, the plan is of another batch shape")
+            plan = None
     dev = next(model.parameters()).device
     ids = input_ids.to(dev, torch.int64).contiguous()
     mask = attention_mask.to(dev, torch.int64).contiguous() if attention_mask is not None else None
@@ -288,9 +365,13 @@ def train_hidden(model, input_ids: torch.Tensor, attention_mask: Optional[torch.
     pa = float(cfg.attention_probs_dropout_prob) if model.training else 0.0
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (ph > 0 or pa > 0) else 0
-    st = _Step(model, _Weights(model, dev), ids, mask, (ph, pa, seed), types)
+    if plan is not None and plan.cu_seqlens.device != dev:
+        plan.cu_seqlens = plan.cu_seqlens.to(dev)
+    st = _Step(model, _Weights(model, dev), ids, mask, (ph, pa, seed), types, plan)
     named, emb, layers = _param_groups(model)
     h = _EmbedFn.apply(ids, st, emb, *[named[n] for n in emb])
     for i, names in enumerate(layers):
         h = _LayerFn.apply(h, st, i, names, *[named[n] for n in names])
+    if plan is not None:
+        h = _UnpackFn.apply(h, st)
     return h.view(B, L, cfg.hidden_size).float()

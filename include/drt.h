@@ -616,6 +616,53 @@ int drt_pool_packed_bf16(const void* hidden, const int32_t* cu_seqlens, int64_t 
 int drt_unpack_rows_bf16(const void* packed, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H,
                          void* out, void* stream);
 /* ------------------------------------------------------------------------
+ * Padding-free BERT training: the attention pair and the copies of a tower that runs on the packed
+ * [T, H] rows (model/train_tower.py).  Whole-sequence kernels only: 1 <= max_len <= 160.  A bad
+ * argument (max_len outside that range, head_dim != 64, drop_p outside [0, 1)) is DRT_EINVAL before
+ * any HIP call; n_seqs == 0 or T == 0 is DRT_OK.
+ * Layouts, with T = cu[B] and W = ceil(longest sequence of the BATCH / 32), the same for every launch
+ * of the batch whatever its max_len:
+ *   lse        fp32 [heads][T]: entry (h, cu[b] + q) is head h, query q of sequence b;
+ *   drop_bits  u32  [heads][T][W]: bit (key & 31) of word (h, cu[b] + q, key >> 5); a launch writes /
+ *              reads the first ceil(max_len / 32) words of each query (W * 32 >= max_len);
+ *   keeps      of (b, head, q, key): the pairwise hash of the padded forward with the row
+ *              (b * heads + head) * L_pad + q, L_pad = the padded length of the batch: for one
+ *              (drop_p, seed, site) every real (q, key) keeps what drt_attention_forward_bf16 keeps on the
+ *              padded batch [B, L_pad].  L_pad >= max_len.
+ * drt_attention_varlen_train_forward_bf16: ctx [T, H] as drt_attention_varlen_forward_bf16 (the same
+ *   bits at drop_p = 0, with or without lse), plus lse (may be NULL) and, with drop_p > 0, dropout of
+ *   the probabilities and the keep words (drop_bits may be NULL).  Sequence lists, clamping and empty
+ *   lengths as the inference entry.
+ * drt_attention_varlen_backward_bf16: dqkv [T, 3H] of the forward above for the listed sequences from
+ *   qkv, ctx, dctx [T, H] and lse; rows of unlisted sequences and rows past max_len of a longer one are
+ *   not touched, a length below 1 writes nothing.  drop_p > 0 reads the forward's drop_bits, or with
+ *   drop_bits == NULL draws the same keeps again.  dsum (may be NULL): fp32 [B][3H], row b receives the
+ *   column sums of sequence b's dqkv rows as stored; drt_colsum_f32 over the B rows, after the last
+ *   launch of a batch, is the q / k / v bias gradient in a fixed order.  A sequence run alone with
+ *   max_len = len has the dqkv bits of drt_attention_backward_bf16 (B = 1, L = len, no mask).
+ * drt_pack_rows_bf16: out [out_rows, H] bf16 = the real rows of padded [B * L, H] in packed order
+ *   (the inverse of drt_unpack_rows_bf16, and its backward), rows cu[B] .. out_rows - 1 zeroed.
+ *   H % 8 == 0, padded and out 16-byte aligned.
+ * drt_embed_ln_pre_packed: drt_embed_ln_packed that also stores the pre-LN sum (pre [T, H] bf16, may
+ *   be NULL) as drt_embed_ln_pre does; each row has the bits of the padded kernel's row.          */
+int drt_attention_varlen_train_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                            int64_t n_seqs, int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                            void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
+                                            int32_t head_dim, float scale, float drop_p, uint64_t seed,
+                                            uint64_t site, void* stream);
+int drt_attention_varlen_backward_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                       const int32_t* cu_seqlens, const int32_t* seq_ids, int64_t n_seqs,
+                                       int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                       const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads,
+                                       int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
+                                       void* stream);
+int drt_pack_rows_bf16(const void* padded, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H, void* out,
+                       int64_t out_rows, void* stream);
+int drt_embed_ln_pre_packed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, int64_t B,
+                            int64_t L, int64_t T, const float* word_emb, const float* pos_emb,
+                            const float* type_emb, const float* gamma, const float* beta, float eps, int32_t H,
+                            void* out, void* pre, void* stream);
+/* ------------------------------------------------------------------------
  * T5 encoder forward building blocks (HF T5EncoderModel in eval mode, modeling_t5.py; pre-norm
  * layer = rmsnorm -> linear(QKV, no bias) -> attention + relative bias -> linear(out, +residual)
  * -> rmsnorm -> linear(FFN1, ReLU | gated gelu_new) -> linear(FFN2, +residual); final rmsnorm).
