@@ -105,6 +105,11 @@ __host__ __device__ __forceinline__ bool attn_keep(uint32_t row_key, int key, ui
 
 constexpr float kLog2e = 1.4426950408889634f;   // softmax in exp2 form (attention kernels)
 
+// Longest sequence of the whole-sequence attention backward (encoder_bwd.hip: Qs, K, V, dO of one
+// sequence in LDS), so also of the varlen training pair; longer padded sequences take the streamed
+// backward.  model/train_tower.py MAX_PACKED_TRAIN_LEN restates it (tests pin the two together).
+constexpr int kAbMaxSeq = 160;
+
 // faiss pads rows that have fewer than k results with label -1 and the
 // lowest float (CMin<float>::neutral() == numeric_limits<float>::lowest()).
 constexpr float kPadScore = -3.402823466e+38f;
@@ -121,5 +126,21 @@ inline int hip_status(hipError_t e) { return e == hipSuccess ? DRT_OK : (int)e; 
   do {                                       \
     if (!(cond)) return DRT_EINVAL;          \
   } while (0)
+
+// Dynamic LDS of a launch: the default limit, and the one allow_large_lds raises a kernel to (once
+// per kernel; the attention launch helpers call it for the images that need it).  static: each
+// unit remembers its own kernels, and the library exports nothing new.  At most 17 kernels can ask
+// (12 backward, 5 forward); past 32, or when two threads race for a slot, a kernel is merely raised
+// again on its next launch.
+constexpr size_t kDefaultLdsBytes = 64 * 1024, kLargeLdsBytes = 160 * 1024;
+static inline hipError_t allow_large_lds(const void* kernel) {
+  static const void* raised[32];
+  static int n = 0;
+  for (int i = 0; i < n; ++i)
+    if (raised[i] == kernel) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLargeLdsBytes);
+  if (e == hipSuccess && n < 32) raised[n++] = kernel;
+  return e;
+}
 
 }  // namespace drt

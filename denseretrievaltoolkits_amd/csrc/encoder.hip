@@ -32,26 +32,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int64_t* ids, const
   const int64_t id = ids[t];
   const int64_t pos = t % L;
   const int64_t tt = type_ids ? type_ids[t] : 0;
-  const float* w = wemb + id * H;
-  const float* p = pemb + pos * H;
-  const float* y = temb + tt * H;
-  float x[EPL];
-#pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const int c = e4 * 256 + lane * 4;
-    const f32x4 a = *(const f32x4*)(w + c);
-    const f32x4 b = *(const f32x4*)(p + c);
-    const f32x4 d = *(const f32x4*)(y + c);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) x[e4 * 4 + u] = (a[u] + d[u]) + b[u];  // (word + type) + position, as HF
-    if (pre) {   // training forward: the pre-LN sum, input of the LayerNorm backward
-      bf16x4 o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (__bf16)x[e4 * 4 + u];
-      *(bf16x4*)(pre + t * H + c) = o;
-    }
-  }
-  ln_row<EPL>(x, gamma, beta, eps, lane, H, out + t * H);
+  embed_ln_row<EPL>(id, tt, pos, t, wemb, pemb, temb, gamma, beta, eps, lane, H, out, pre);
 }
 
 // erf GELU, elementwise (the training forward keeps FFN1's pre-activation for the backward)
@@ -614,6 +595,23 @@ __global__ __launch_bounds__(256) void l2norm_kernel(float* x, int64_t B, int H,
   }
 }
 
+// Launch of attention_fwd_kernel for sequences of at most `len` tokens (L, or a varlen launch's
+// max_len), one work-group per (sequence, head) group: the one place that knows the length class NB,
+// the LDS image (K rows, V^T, key bias, and the staged relative bias with `rb`) and the block size.
+// `pick(NB)` names the caller's instantiation of the class (NB = 0: len > 160), so a new
+// instantiation is one more entry in its caller's table and no launch code.
+template <typename Pick>
+static int launch_attention_fwd(Pick&& pick, AttnArgs& a, int len, bool rb, int64_t groups, void* stream) {
+  const int Lp = (len + 31) & ~31;
+  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
+  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (rb ? (size_t)Lp * 8 : 0);
+  const void* kernel = (const void*)pick(nb);
+  if (lds > kDefaultLdsBytes) DRT_CHECK_HIP(allow_large_lds(kernel));   // len > 224 (NB = 0 only)
+  void* args[] = {&a};
+  hipLaunchKernel(kernel, dim3((unsigned)groups), dim3(nb == 5 ? 320 : 256), args, lds, (hipStream_t)stream);
+  return hip_status(hipGetLastError());
+}
+
 }  // namespace drt
 
 using namespace drt;
@@ -727,21 +725,7 @@ int drt_attention_forward_bf16(const void* qkv, const int64_t* mask, const float
                                               DRT_AF_ROW(3), DRT_AF_ROW(4), DRT_AF_ROW(5)};
 #undef DRT_AF_ROW
   const bool drop = drop_p > 0.0f, rb = relbias != nullptr;
-  const int Lp = ((int)L + 31) & ~31;
-  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (rb ? (size_t)Lp * 8 : 0);
-  static bool attr_set = false;
-  if (!attr_set) {   // L > 224 stages more than the default 64 KiB
-    for (const auto& by_drop : kernels)
-      for (const auto& by_rb : by_drop)
-        for (const Kernel k : by_rb)
-          DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  void* args[] = {&a};
-  hipLaunchKernel((const void*)kernels[nb][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
-                  (hipStream_t)stream);
-  return hip_status(hipGetLastError());
+  return launch_attention_fwd([&](int nb) { return kernels[nb][drop][rb]; }, a, (int)L, rb, B * heads, stream);
 }
 
 // The forward over a packed batch (contract: drt.h): the VL instantiations, one work-group per
@@ -761,19 +745,7 @@ int drt_attention_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens
       attention_fwd_kernel<0, false, false, 1>, attention_fwd_kernel<1, false, false, 1>,
       attention_fwd_kernel<2, false, false, 1>, attention_fwd_kernel<3, false, false, 1>,
       attention_fwd_kernel<4, false, false, 1>, attention_fwd_kernel<5, false, false, 1>};
-  const int Lp = ((int)max_len + 31) & ~31;
-  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;
-  static bool attr_set = false;
-  if (!attr_set) {   // max_len > 224 stages more than the default 64 KiB
-    for (const Kernel k : kernels)
-      DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  void* args[] = {&a};
-  hipLaunchKernel((const void*)kernels[nb], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 320 : 256), args, lds,
-                  (hipStream_t)stream);
-  return hip_status(hipGetLastError());
+  return launch_attention_fwd([&](int nb) { return kernels[nb]; }, a, max_len, false, n_seqs * heads, stream);
 }
 
 // The training forward over a packed batch (contract: drt.h): VL x {plain, DROP} at the five
@@ -785,8 +757,7 @@ int drt_attention_varlen_train_forward_bf16(const void* qkv, const int32_t* cu_s
                                             void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
                                             int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
                                             void* stream) {
-  constexpr int kMaxTrainLen = 160;
-  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kMaxTrainLen && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kAbMaxSeq && heads > 0 && head_dim == kHeadDim);
   DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
   DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
   if (n_seqs == 0 || T == 0) return DRT_OK;
@@ -802,13 +773,8 @@ int drt_attention_varlen_train_forward_bf16(const void* qkv, const int32_t* cu_s
       {attention_fwd_kernel<3, false, false, 2>, attention_fwd_kernel<3, true, false, 2>},
       {attention_fwd_kernel<4, false, false, 2>, attention_fwd_kernel<4, true, false, 2>},
       {attention_fwd_kernel<5, false, false, 2>, attention_fwd_kernel<5, true, false, 2>}};
-  const int Lp = ((int)max_len + 31) & ~31;
-  const int nb = Lp / 32;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;   // <= 42 KiB
-  void* args[] = {&a};
-  hipLaunchKernel((const void*)kernels[nb - 1][drop], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 320 : 256), args,
-                  lds, (hipStream_t)stream);
-  return hip_status(hipGetLastError());
+  // max_len <= kAbMaxSeq: NB is 1 .. 5
+  return launch_attention_fwd([&](int nb) { return kernels[nb - 1][drop]; }, a, max_len, false, n_seqs * heads, stream);
 }
 
 // The earlier names (drt.h, "Earlier attention names"): argument subsets of the entry above.

@@ -282,9 +282,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const __bf16* x, in
 // 32x32x16 MFMA: A lane (m = l & 31, h = l >> 5) holds A[m][k = 8h .. 8h + 7]; B lane (n, h) holds
 // B[k = 8h ..][n]; D lane (n = l & 31, h) holds D[m = 8 (e >> 2) + 4 h + (e & 3)][n].
 // ---------------------------------------------------------------------------
-constexpr int kAbMaxSeq = 160;
-constexpr int kAbRow = 128;               // bytes per [.][64] bf16 row
-
+constexpr int kAbRow = 128;               // bytes per [.][64] bf16 row  (kAbMaxSeq: drt_common.h)
 
 struct AttnBwdArgs {
   const __bf16* qkv;     // [B*L][3H]
@@ -1326,6 +1324,27 @@ static int64_t attention_bwd_rows(int64_t B, int64_t L) {
   return L > kAbMaxSeq ? B * ((L + kAblGroup - 1) / kAblGroup) : B;
 }
 
+// Launch of the whole-sequence backward kernel (attention_bwd_rk_kernel) for sequences of at most
+// `len` <= kAbMaxSeq tokens, one work-group per (sequence, head) group: the one place that knows the
+// length class, the LDS image and the block size.  `pick(NB)` names the caller's instantiation of the
+// class, so a new instantiation is one more entry in its caller's table and no launch code.
+template <typename Pick>
+static int launch_attention_bwd_rk(Pick&& pick, AttnBwdArgs& a, int len, bool drop, bool rb, int64_t groups,
+                                   hipStream_t stream) {
+  const int Lp = (len + 31) & ~31;
+  const int nb = Lp / 32;
+  // register-resident P / dS; dropout from the forward's keep bits (or the same bits drawn again)
+  const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + 32 + (drop ? (size_t)nb * Lp * 4 : 0) +
+                     (rb ? (size_t)4 * Lp * 4 + (size_t)4 * (2 * Lp + 4) * 4 : 0);   // RB: the bias diagonals and
+                                              // their gradient, 2 Lp floats each, + 4 shifted reversed copies
+  DRT_REQUIRE(lds <= kLargeLdsBytes);
+  const void* kernel = (const void*)pick(nb);
+  if (lds > kDefaultLdsBytes) DRT_CHECK_HIP(allow_large_lds(kernel));   // from NB = 4 up
+  void* args[] = {&a};
+  hipLaunchKernel(kernel, dim3((unsigned)groups), dim3(nb == 5 ? 512 : 256), args, lds, stream);
+  return hip_status(hipGetLastError());
+}
+
 }  // namespace drt
 
 using namespace drt;
@@ -1455,32 +1474,17 @@ int drt_attention_backward_bf16(const void* qkv, const void* ctx, const void* dc
 #undef DRT_AB_LONG
   const bool drop = drop_p > 0.0f, rb = relbias != nullptr;
   hipStream_t st = (hipStream_t)stream;
-  void* args[] = {&a};
+  int rc;
   if (L > kAbMaxSeq) {   // streamed kernels: dK / dV over key groups, dQ over query groups
     DRT_REQUIRE(!drop || drop_bits);   // the forward's keep bits
+    void* args[] = {&a};
     const dim3 grid((unsigned)(B * heads), (unsigned)((L + kAblGroup - 1) / kAblGroup));
     hipLaunchKernel((const void*)long_dkdv[drop][rb], grid, dim3(256), args, 0, st);
     hipLaunchKernel((const void*)long_dq[drop][rb], grid, dim3(256), args, 0, st);
+    rc = hip_status(hipGetLastError());
   } else {
-    const int Lp = ((int)L + 31) & ~31;
-    const int nb = Lp / 32;
-    // register-resident P / dS; dropout from the forward's keep bits (or the same bits drawn again)
-    const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + 32 + (drop ? (size_t)nb * Lp * 4 : 0) +
-                       (rb ? (size_t)4 * Lp * 4 + (size_t)4 * (2 * Lp + 4) * 4 : 0);   // RB: the bias diagonals and
-                                                // their gradient, 2 Lp floats each, + 4 shifted reversed copies
-    DRT_REQUIRE(lds <= 160 * 1024);
-    static bool rk_attr = false;
-    if (!rk_attr) {
-      for (const auto& by_drop : rk)
-        for (const auto& by_rb : by_drop)
-          for (const Kernel k : by_rb)
-            DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      rk_attr = true;
-    }
-    hipLaunchKernel((const void*)rk[nb - 1][drop][rb], dim3((unsigned)(B * heads)), dim3(nb == 5 ? 512 : 256), args,
-                    lds, st);
+    rc = launch_attention_bwd_rk([&](int nb) { return rk[nb - 1][drop][rb]; }, a, (int)L, drop, rb, B * heads, st);
   }
-  const int rc = hip_status(hipGetLastError());
   if (rc || !part) return rc;
   const int64_t rows = attention_bwd_rows(B, L);
   if (dbias) {
@@ -1515,20 +1519,8 @@ int drt_attention_varlen_backward_bf16(const void* qkv, const void* ctx, const v
 #define DRT_AB_VL(NB) {attention_bwd_rk_kernel<NB, false, false, true>, attention_bwd_rk_kernel<NB, true, false, true>}
   static constexpr Kernel vl[5][2] = {DRT_AB_VL(1), DRT_AB_VL(2), DRT_AB_VL(3), DRT_AB_VL(4), DRT_AB_VL(5)};
 #undef DRT_AB_VL
-  const int Lp = ((int)max_len + 31) & ~31;
-  const int nb = Lp / 32;
-  const size_t lds = (size_t)4 * Lp * kAbRow + (size_t)3 * Lp * 4 + 32 + (drop ? (size_t)nb * Lp * 4 : 0);
-  static bool vl_attr = false;
-  if (!vl_attr) {   // NB = 5 stages more than the default 64 KiB
-    for (const auto& by_drop : vl)
-      for (const Kernel k : by_drop)
-        DRT_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    vl_attr = true;
-  }
-  void* args[] = {&a};
-  hipLaunchKernel((const void*)vl[nb - 1][drop], dim3((unsigned)(n_seqs * heads)), dim3(nb == 5 ? 512 : 256), args, lds,
-                  (hipStream_t)stream);
-  return hip_status(hipGetLastError());
+  return launch_attention_bwd_rk([&](int nb) { return vl[nb - 1][drop]; }, a, max_len, drop, false, n_seqs * heads,
+                                 (hipStream_t)stream);
 }
 
 // The earlier names (drt.h, "Earlier attention names"): argument subsets of the two entries above.

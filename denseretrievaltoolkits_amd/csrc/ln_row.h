@@ -39,6 +39,36 @@ __device__ __forceinline__ void ln_row(float (&x)[EPL], const float* gamma, cons
   }
 }
 
+// One row of BertEmbeddings (modeling_bert.py:68-108) for the wave: out row t = LayerNorm(word[id] +
+// type[tt] + position[pos]), fp32; shared by embed_ln_kernel (encoder.hip: t = b L + pos) and
+// embed_ln_packed_kernel (packed.hip: t the packed row of token (b, pos)), which differ only in how
+// they find (id, tt, pos) -- so packed and padded rows agree bit for bit.
+template <int EPL>
+__device__ __forceinline__ void embed_ln_row(int64_t id, int64_t tt, int64_t pos, int64_t t, const float* wemb,
+                                             const float* pemb, const float* temb, const float* gamma,
+                                             const float* beta, float eps, int lane, int H, __bf16* out, __bf16* pre) {
+  const float* w = wemb + id * H;
+  const float* p = pemb + pos * H;
+  const float* y = temb + tt * H;
+  float x[EPL];
+#pragma unroll
+  for (int e4 = 0; e4 < EPL / 4; ++e4) {
+    const int c = e4 * 256 + lane * 4;
+    const f32x4 a = *(const f32x4*)(w + c);
+    const f32x4 b = *(const f32x4*)(p + c);
+    const f32x4 d = *(const f32x4*)(y + c);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[e4 * 4 + u] = (a[u] + d[u]) + b[u];  // (word + type) + position, as HF
+    if (pre) {   // training forward: the pre-LN sum, input of the LayerNorm backward
+      bf16x4 o;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) o[u] = (__bf16)x[e4 * 4 + u];
+      *(bf16x4*)(pre + t * H + c) = o;
+    }
+  }
+  ln_row<EPL>(x, gamma, beta, eps, lane, H, out + t * H);
+}
+
 // ln_row with gamma / beta already in registers (g[e], b[e] of column (e / 4) * 256 + lane * 4 + e % 4):
 // the same arithmetic in the same order, for kernels that normalise many rows per wave.
 template <int EPL>

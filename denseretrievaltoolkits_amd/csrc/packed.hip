@@ -3,8 +3,8 @@
 // cu_seqlens (int32 [B + 1], cu[0] = 0, cu[B] = T) says where each sequence starts.  The GEMMs and
 // LayerNorm take any row count, so only the kernels that know about (sequence, position) differ:
 //
-//   embed_ln_packed   packed row t = token (b, t - cu[b]) of the padded ids [B, L]; the arithmetic
-//                     of embed_ln_kernel (encoder.hip) per row, bit for bit
+//   embed_ln_packed   packed row t = token (b, t - cu[b]) of the padded ids [B, L]; the row itself is
+//                     embed_ln_row (ln_row.h), the function embed_ln_kernel (encoder.hip) calls
 //   pool_packed       first / mean / max over a sequence's len rows (max gives 0 when len < L: the
 //                     reference's max(hidden * mask), utils.py:233-240, sees a zero at every pad)
 //   unpack_rows       [T, H] -> [B * L, H] with zeros at the pad positions
@@ -42,26 +42,7 @@ __global__ __launch_bounds__(256) void embed_ln_packed_kernel(const int64_t* ids
   const int64_t src = (int64_t)b * L + pos;
   const int64_t id = ids[src];
   const int64_t tt = type_ids ? type_ids[src] : 0;
-  const float* w = wemb + id * H;
-  const float* p = pemb + pos * H;
-  const float* y = temb + tt * H;
-  float x[EPL];
-#pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const int c = e4 * 256 + lane * 4;
-    const f32x4 a = *(const f32x4*)(w + c);
-    const f32x4 bb = *(const f32x4*)(p + c);
-    const f32x4 d = *(const f32x4*)(y + c);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) x[e4 * 4 + u] = (a[u] + d[u]) + bb[u];  // (word + type) + position, as HF
-    if (pre) {   // training forward: the pre-LN sum, input of the LayerNorm backward
-      bf16x4 o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (__bf16)x[e4 * 4 + u];
-      *(bf16x4*)(pre + t * H + c) = o;
-    }
-  }
-  ln_row<EPL>(x, gamma, beta, eps, lane, H, out + t * H);
+  embed_ln_row<EPL>(id, tt, pos, t, wemb, pemb, temb, gamma, beta, eps, lane, H, out, pre);
 }
 
 __global__ __launch_bounds__(256) void pool_packed_kernel(const __bf16* hidden, const int32_t* cu, int64_t L, int H,

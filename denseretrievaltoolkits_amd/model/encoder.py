@@ -30,6 +30,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import _native
+from .encoder_bwd import unpack_rows
 
 POOL_MODES = {"first": 0, "mean": 1, "max": 2}
 
@@ -60,6 +61,70 @@ def _check_supported(shape: BertShape):
         raise ValueError(f"activation {shape.act} unsupported (erf GELU only)")
     if shape.act != "gelu":
         raise ValueError("only erf GELU ('gelu') is implemented")
+
+
+def linear_ws(lib, x, w, b, resid, out, flags, ws, stream):
+    """out = act(x w^T + b) (+ resid) through drt_linear_bf16_ws with the caller's split-K scratch ``ws``
+    (fp32 tensor or None): the ``_lin`` of every inference encoder / decoder."""
+    m, k = x.shape
+    _native.check(lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
+                                         resid.data_ptr() if resid is not None else None, out.data_ptr(),
+                                         m, w.shape[0], k, flags, ws.data_ptr() if ws is not None else None,
+                                         ws.numel() * 4 if ws is not None else 0, stream), "drt_linear_bf16_ws")
+    return out
+
+
+def bert_weights(sd: Dict[str, torch.Tensor], dev, layers: int, prefix: str = ""):
+    """The weight snapshot of a BertModel state dict (HF names), for the inference encoder and the
+    training tower alike: ((word, pos, type, emb_g, emb_b) fp32, one dict per layer with bf16
+    ``wqkv / wo / wi / wf`` and fp32 biases and LayerNorm ``bqkv, bo, g1, b1, bi, bf, g2, b2``).  Q | K | V
+    are concatenated in fp32 and rounded to bf16 once."""
+    def f32(name):
+        return sd[prefix + name].detach().to(dev, torch.float32).contiguous()
+
+    def b16(name):
+        return sd[prefix + name].detach().to(dev, torch.float32).to(torch.bfloat16).contiguous()
+
+    def qkv(p, kind):
+        return torch.cat([sd[prefix + p + f"attention.self.{n}.{kind}"].detach().float()
+                          for n in ("query", "key", "value")], 0).to(dev)
+
+    e = "embeddings."
+    emb = (f32(e + "word_embeddings.weight"), f32(e + "position_embeddings.weight"),
+           f32(e + "token_type_embeddings.weight"), f32(e + "LayerNorm.weight"), f32(e + "LayerNorm.bias"))
+    out = []
+    for i in range(layers):
+        p = f"encoder.layer.{i}."
+        out.append(dict(
+            wqkv=qkv(p, "weight").to(torch.bfloat16).contiguous(), bqkv=qkv(p, "bias").contiguous(),
+            wo=b16(p + "attention.output.dense.weight"), bo=f32(p + "attention.output.dense.bias"),
+            g1=f32(p + "attention.output.LayerNorm.weight"), b1=f32(p + "attention.output.LayerNorm.bias"),
+            wi=b16(p + "intermediate.dense.weight"), bi=f32(p + "intermediate.dense.bias"),
+            wf=b16(p + "output.dense.weight"), bf=f32(p + "output.dense.bias"),
+            g2=f32(p + "output.LayerNorm.weight"), b2=f32(p + "output.LayerNorm.bias"),
+        ))
+    return emb, out
+
+
+# Two parts of a batch on two HIP streams: one part's memory-bound kernels (attention, LayerNorm) and
+# GEMM tails overlap the other part's GEMMs (+4.4 % on the encode leg, tools/enc_streams.py).  Same
+# kernels per part -> bit-identical to one pass.  Whatever the parts share (T5's bias table) is built by
+# the caller on the launch stream, before the fork.
+def run_on_two_streams(enc, out: torch.Tensor, parts):
+    """``parts``: two (run, rows) pairs; ``run(out[rows])`` fills that slice of ``out`` on its own stream
+    (``enc._streams``, made on first use), forked from and joined back into the current stream."""
+    dev = enc.device
+    cur = torch.cuda.current_stream(dev)
+    if enc._streams is None:
+        enc._streams = [torch.cuda.Stream(dev) for _ in range(2)]
+    for st, (run, rows) in zip(enc._streams, parts):
+        st.wait_stream(cur)
+        with torch.cuda.stream(st):
+            run(out[rows])
+        out.record_stream(st)
+    for st in enc._streams:
+        cur.wait_stream(st)
+    return out
 
 
 class HipBertEncoder:
@@ -99,35 +164,8 @@ class HipBertEncoder:
 
     # -- weights --------------------------------------------------------
     def _load(self, sd: Dict[str, torch.Tensor], prefix: str):
-        dev = self.device
-
-        def f32(name):
-            return sd[prefix + name].detach().to(dev, torch.float32).contiguous()
-
-        def b16(name):
-            return sd[prefix + name].detach().to(dev, torch.float32).to(torch.bfloat16).contiguous()
-
-        self.word = f32("embeddings.word_embeddings.weight")
-        self.pos = f32("embeddings.position_embeddings.weight")
-        self.type = f32("embeddings.token_type_embeddings.weight")
-        self.emb_g = f32("embeddings.LayerNorm.weight")
-        self.emb_b = f32("embeddings.LayerNorm.bias")
-        self.layers = []
-        for i in range(self.shape.layers):
-            p = f"encoder.layer.{i}."
-            wqkv = torch.cat([sd[prefix + p + f"attention.self.{n}.weight"].detach().float()
-                              for n in ("query", "key", "value")], 0)
-            bqkv = torch.cat([sd[prefix + p + f"attention.self.{n}.bias"].detach().float()
-                              for n in ("query", "key", "value")], 0)
-            self.layers.append(dict(
-                wqkv=wqkv.to(dev).to(torch.bfloat16).contiguous(),
-                bqkv=bqkv.to(dev).contiguous(),
-                wo=b16(p + "attention.output.dense.weight"), bo=f32(p + "attention.output.dense.bias"),
-                g1=f32(p + "attention.output.LayerNorm.weight"), b1=f32(p + "attention.output.LayerNorm.bias"),
-                wi=b16(p + "intermediate.dense.weight"), bi=f32(p + "intermediate.dense.bias"),
-                wf=b16(p + "output.dense.weight"), bf=f32(p + "output.dense.bias"),
-                g2=f32(p + "output.LayerNorm.weight"), b2=f32(p + "output.LayerNorm.bias"),
-            ))
+        emb, self.layers = bert_weights(sd, self.device, self.shape.layers, prefix)
+        self.word, self.pos, self.type, self.emb_g, self.emb_b = emb
 
     @classmethod
     def from_hf(cls, model, device, presum: str = "bf16") -> "HipBertEncoder":
@@ -136,16 +174,8 @@ class HipBertEncoder:
 
     # -- forward --------------------------------------------------------
     def _lin(self, x, w, b, out, resid=None, gelu=False):
-        m, k = x.shape
-        n = w.shape[0]
         flags = (1 if gelu else 0) | (2 if out.dtype == torch.float32 else 0)
-        ws = self._ws
-        _native.check(self.lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
-                                                  resid.data_ptr() if resid is not None else None, out.data_ptr(),
-                                                  m, n, k, flags, ws.data_ptr() if ws is not None else None,
-                                                  ws.numel() * 4 if ws is not None else 0, self.stream),
-                      "drt_linear_bf16_ws")
-        return out
+        return linear_ws(self.lib, x, w, b, resid, out, flags, self._ws, self.stream)
 
     def _lin_ln(self, x, w, b, h, g, beta, x32, ln):
         """h = LayerNorm(x w^T + b + h) (BertSelfOutput / BertOutput, modeling_bert.py:282-352).  bf16
@@ -190,32 +220,21 @@ class HipBertEncoder:
             return self._replay(ids, mask, tt)
         if (self.split_streams and B >= 2 and B * L >= self.split_min_tokens
                 and not torch.cuda.is_current_stream_capturing()):
-            return self._run_halves(ids, mask, tt)
+            half = B // 2
+            parts = [(0, half, None, slice(0, half * L)), (half, B, None, slice(half * L, B * L))]
+            return self._run_parts(ids, mask, tt, B * L, parts).view(B, L, -1)
         return self._run(ids, mask, tt)
 
-    # -- two halves on two streams ----------------------------------------
-    # Large batches run as two independent halves on two HIP streams: one half's memory-bound
-    # kernels (attention, LayerNorm) and GEMM tails overlap the other half's GEMMs (+4.4 % on the
-    # encode leg, tools/enc_streams.py).  Same kernels per half -> bit-identical to one pass.
-    def _run_halves(self, ids, mask, tt):
-        dev = self.device
-        B, L = ids.shape
-        H = self.shape.hidden
-        out = torch.empty((B * L, H), dtype=torch.bfloat16, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        if self._streams is None:
-            self._streams = [torch.cuda.Stream(dev) for _ in range(2)]
-        half = B // 2
-        for i, (a, b) in enumerate(((0, half), (half, B))):
-            st = self._streams[i]
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                self._run(ids[a:b], mask[a:b] if mask is not None else None, tt[a:b] if tt is not None else None,
-                          out=out[a * L:b * L])
-            out.record_stream(st)
-        for st in self._streams:
-            cur.wait_stream(st)
-        return out.view(B, L, H)
+    def _run_parts(self, ids, mask, tt, rows, parts):
+        """[rows, H] from two _run calls on two streams (run_on_two_streams); ``parts``: (first sequence,
+        end sequence, plan or None, output rows) of each."""
+        def part(b0, b1, plan):
+            def cut(t):
+                return t[b0:b1] if t is not None else None
+            return lambda out: self._run(ids[b0:b1], cut(mask), cut(tt), plan=plan, out=out)
+
+        out = torch.empty((rows, self.shape.hidden), dtype=torch.bfloat16, device=self.device)
+        return run_on_two_streams(self, out, [(part(b0, b1, plan), sl) for b0, b1, plan, sl in parts])
 
     # -- hipGraph replay ------------------------------------------------
     # Small batches (queries: 128 x 32 tokens) are host-bound: 1 + 7 x layers launches through
@@ -252,17 +271,25 @@ class HipBertEncoder:
         g.replay()
         return out.clone()
 
-    def _run(self, ids, mask, tt, out=None):
+    def _run(self, ids, mask, tt, plan=None, out=None):
+        """The layer loop.  Padded: ``[B, L, H]`` over the rectangle.  With ``plan`` (model/packing.py): the
+        packed embedding and the varlen attention over the plan's T real tokens, ``[T, H]``; no mask."""
         sh = self.shape
         dev = self.device
         B, L = ids.shape
-        H, T = sh.hidden, B * L
+        H = sh.hidden
+        T = plan.T if plan is not None else B * L
         self.stream = _native.stream_ptr(dev)
         h = out if out is not None else torch.empty((T, H), dtype=torch.bfloat16, device=dev)
-        _native.check(self.lib.drt_embed_ln(ids.data_ptr(), tt.data_ptr() if tt is not None else None, B, L,
-                                            self.word.data_ptr(), self.pos.data_ptr(), self.type.data_ptr(),
-                                            self.emb_g.data_ptr(), self.emb_b.data_ptr(), sh.eps, H, h.data_ptr(),
-                                            self.stream), "drt_embed_ln")
+        emb = (self.word.data_ptr(), self.pos.data_ptr(), self.type.data_ptr(), self.emb_g.data_ptr(),
+               self.emb_b.data_ptr(), sh.eps, H, h.data_ptr(), self.stream)
+        ttp = tt.data_ptr() if tt is not None else None
+        if plan is not None:
+            cu = plan.cu_seqlens.data_ptr()
+            launches = plan.launches(self.packed_classes)
+            _native.check(self.lib.drt_embed_ln_packed(ids.data_ptr(), ttp, cu, B, L, T, *emb), "drt_embed_ln_packed")
+        else:
+            _native.check(self.lib.drt_embed_ln(ids.data_ptr(), ttp, B, L, *emb), "drt_embed_ln")
         qkv = torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev)
         ctx = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
         f32 = self.presum == "fp32"
@@ -275,21 +302,27 @@ class HipBertEncoder:
         mp = mask.data_ptr() if mask is not None else None
         for ly in self.layers:
             self._lin(h, ly["wqkv"], ly["bqkv"], qkv)
-            _native.check(self.lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, None, ctx.data_ptr(), None, None, B, L,
-                                                              sh.heads, H // sh.heads, scale, 0.0, 0, 0, self.stream),
-                          "drt_attention_forward_bf16")
+            if plan is None:
+                _native.check(self.lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, None, ctx.data_ptr(), None, None,
+                                                                  B, L, sh.heads, H // sh.heads, scale, 0.0, 0, 0,
+                                                                  self.stream), "drt_attention_forward_bf16")
+            else:
+                for sp, n, ml in launches:
+                    _native.check(self.lib.drt_attention_varlen_forward_bf16(
+                        qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(), sh.heads, H // sh.heads, scale, self.stream),
+                        "drt_attention_varlen_forward_bf16")
             self._lin_ln(ctx, ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], x32, ln)
             self._lin(h, ly["wi"], ly["bi"], ffn, gelu=True)
             self._lin_ln(ffn, ly["wf"], ly["bf"], h, ly["g2"], ly["b2"], x32, ln)
-        return h.view(B, L, H)
+        return h if plan is not None else h.view(B, L, H)
 
     __call__ = forward
 
     # -- padding-free inference ---------------------------------------------
-    # Only the T real tokens of the batch are computed (model/packing.py): the layer loop of _run
-    # over [T, H] matrices, with the packed embedding and the varlen attention (one launch per
-    # length class of the plan, so a long sequence does not set the short ones' LDS footprint).  No
-    # graph replay.
+    # Only the T real tokens of the batch are computed (model/packing.py): _run with the batch's plan,
+    # i.e. [T, H] matrices, the packed embedding and the varlen attention (with packed_classes one
+    # launch per length class of the plan, so a long sequence does not set the short ones' LDS
+    # footprint).  No graph replay.
     def forward_packed(self, input_ids: torch.Tensor, plan, token_type_ids: Optional[torch.Tensor] = None
                        ) -> torch.Tensor:
         """last_hidden_state of the real tokens, [T, H] bf16 in the plan's packed order."""
@@ -303,60 +336,12 @@ class HipBertEncoder:
         tt = token_type_ids.to(dev, torch.int64).contiguous() if token_type_ids is not None else None
         if (self.packed_split_streams and B >= 2 and plan.T >= self.split_min_tokens
                 and not torch.cuda.is_current_stream_capturing()):
-            return self._run_packed_halves(ids, plan, tt)
-        return self._run_packed(ids, plan, tt)
-
-    def _run_packed_halves(self, ids, plan, tt):
-        dev = self.device
-        out = torch.empty((plan.T, self.shape.hidden), dtype=torch.bfloat16, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        if self._streams is None:
-            self._streams = [torch.cuda.Stream(dev) for _ in range(2)]
-        row = 0
-        for st, (b0, sub) in zip(self._streams, plan.halves()):
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                self._run_packed(ids[b0:b0 + sub.B], sub, tt[b0:b0 + sub.B] if tt is not None else None,
-                                 out=out[row:row + sub.T])
-            out.record_stream(st)
-            row += sub.T
-        for st in self._streams:
-            cur.wait_stream(st)
-        return out
-
-    def _run_packed(self, ids, plan, tt, out=None):
-        sh = self.shape
-        dev = self.device
-        B, L = ids.shape
-        H, T = sh.hidden, plan.T
-        self.stream = _native.stream_ptr(dev)
-        cu = plan.cu_seqlens.data_ptr()
-        h = out if out is not None else torch.empty((T, H), dtype=torch.bfloat16, device=dev)
-        _native.check(self.lib.drt_embed_ln_packed(ids.data_ptr(), tt.data_ptr() if tt is not None else None, cu, B, L, T,
-                                                   self.word.data_ptr(), self.pos.data_ptr(), self.type.data_ptr(),
-                                                   self.emb_g.data_ptr(), self.emb_b.data_ptr(), sh.eps, H,
-                                                   h.data_ptr(), self.stream), "drt_embed_ln_packed")
-        qkv = torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev)
-        ctx = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
-        f32 = self.presum == "fp32"
-        x32 = torch.empty((T, H), dtype=torch.float32 if f32 else torch.bfloat16, device=dev)
-        ln = self.lib.drt_layernorm_f32_bf16 if f32 else self.lib.drt_layernorm_bf16
-        ffn = torch.empty((T, sh.intermediate), dtype=torch.bfloat16, device=dev)
-        nb = self._ws_bytes(T)
-        self._ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev) if nb else None
-        scale = 1.0 / math.sqrt(H // sh.heads)
-        launches = plan.classes() if self.packed_classes else [(None, B, plan.max_len)]
-        launches = [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]
-        for ly in self.layers:
-            self._lin(h, ly["wqkv"], ly["bqkv"], qkv)
-            for sp, n, ml in launches:
-                _native.check(self.lib.drt_attention_varlen_forward_bf16(qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(),
-                                                                         sh.heads, H // sh.heads, scale, self.stream),
-                              "drt_attention_varlen_forward_bf16")
-            self._lin_ln(ctx, ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], x32, ln)
-            self._lin(h, ly["wi"], ly["bi"], ffn, gelu=True)
-            self._lin_ln(ffn, ly["wf"], ly["bf"], h, ly["g2"], ly["b2"], x32, ln)
-        return h
+            parts, row = [], 0
+            for b0, sub in plan.halves():
+                parts.append((b0, b0 + sub.B, sub, slice(row, row + sub.T)))
+                row += sub.T
+            return self._run_parts(ids, None, tt, plan.T, parts)
+        return self._run(ids, None, tt, plan=plan)
 
     def pool_packed(self, hidden: torch.Tensor, plan, L: int, pooling: str, want_bf16: bool = False):
         """pool() over a packed [T, H] hidden state: the same reps (max pooling keeps the reference's
@@ -375,12 +360,9 @@ class HipBertEncoder:
 
     def unpack(self, hidden: torch.Tensor, plan, L: int) -> torch.Tensor:
         """[B, L, H] bf16 from packed [T, H]: the real tokens at their positions, zeros at the pads."""
-        T, H = hidden.shape
-        out = torch.empty((plan.B, L, H), dtype=torch.bfloat16, device=hidden.device)
-        _native.check(self.lib.drt_unpack_rows_bf16(hidden.data_ptr(), plan.cu_seqlens.data_ptr(), plan.B, L, H,
-                                                    out.data_ptr(), _native.stream_ptr(hidden.device)),
-                      "drt_unpack_rows_bf16")
-        return out
+        if L != plan.L:
+            raise ValueError(f"plan of a [{plan.B}, {plan.L}] batch unpacked to length {L}")
+        return unpack_rows(hidden, plan).view(plan.B, L, hidden.shape[1])
 
     def pool(self, hidden: torch.Tensor, attention_mask: Optional[torch.Tensor], pooling: str,
              want_bf16: bool = False):

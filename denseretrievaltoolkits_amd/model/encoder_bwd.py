@@ -116,13 +116,6 @@ def attention_backward(qkv, ctx, dctx, lse, mask, bits, B, L, heads, scale, relb
     return dqkv, extra
 
 
-def varlen_launches(plan, per_class: bool):
-    """The (seq_ids pointer or None, n_seqs, max_len) of each attention launch over a packed batch: one
-    per length class of the plan, or one for the whole batch."""
-    launches = plan.classes() if per_class else [(None, plan.B, plan.max_len)]
-    return [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]
-
-
 def attention_varlen_forward(qkv, plan, heads, scale, drop=None, per_class=False):
     """(ctx bf16 [rows, heads*64], lse fp32 [heads, T], keep bits [heads, T, W] or None) of the attention
     over the packed ``qkv`` [rows >= T, 3 heads*64] of ``plan`` (model/packing.py); rows past T of ctx
@@ -139,7 +132,7 @@ def attention_varlen_forward(qkv, plan, heads, scale, drop=None, per_class=False
     W = (plan.max_len + 31) // 32
     bits = torch.empty((heads, T, W), dtype=torch.int32, device=dev) if p > 0 else None
     s = _native.stream_ptr(dev)
-    for sp, n, ml in varlen_launches(plan, per_class):
+    for sp, n, ml in plan.launches(per_class):
         _native.check(lib.drt_attention_varlen_train_forward_bf16(
             qkv.data_ptr(), plan.cu_seqlens.data_ptr(), sp, n, ml, plan.L, T, W, ctx.data_ptr(), lse.data_ptr(),
             _ptr(bits), heads, 64, float(scale), float(p), seed, site, s), "drt_attention_varlen_train_forward_bf16")
@@ -161,7 +154,7 @@ def attention_varlen_backward(qkv, ctx, dctx, lse, bits, plan, heads, scale, dro
     p, seed, site = drop if drop is not None else (0.0, 0, 0)
     W = (plan.max_len + 31) // 32
     s = _native.stream_ptr(dev)
-    for sp, n, ml in varlen_launches(plan, per_class):
+    for sp, n, ml in plan.launches(per_class):
         _native.check(lib.drt_attention_varlen_backward_bf16(
             qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), plan.cu_seqlens.data_ptr(), sp, n, ml,
             plan.L, T, W, _ptr(bits), dqkv.data_ptr(), dsum.data_ptr(), heads, 64, float(scale), float(p), seed, site,

@@ -88,6 +88,13 @@ class PackingPlan:
                 self._classes = out
         return self._classes
 
+    def launches(self, per_class: bool):
+        """The (seq_ids pointer or None, n_seqs, max_len) of each varlen attention launch over the batch,
+        forward or backward: one per length class (``classes()``), or one for the whole batch.  Callers
+        build it once per pass, outside their layer loop."""
+        launches = self.classes() if per_class else [(None, self.B, self.max_len)]
+        return [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]
+
 
 def _plan_from_lens(lens: List[int], L: int, device, min_saving: float, force: bool) -> Optional[PackingPlan]:
     B = len(lens)

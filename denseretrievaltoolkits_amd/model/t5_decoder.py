@@ -33,6 +33,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from .. import _native
+from .encoder import linear_ws
 from .t5_encoder import LIN_RELU, HipT5Encoder, T5Shape
 
 MAX_HEADS = 16
@@ -136,14 +137,7 @@ class HipT5PairScorer:
 
     # -- forward --------------------------------------------------------
     def _lin(self, x, w, out, resid=None, flags=0):
-        m, k = x.shape
-        ws = self._ws
-        _native.check(self.lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), None,
-                                                  resid.data_ptr() if resid is not None else None, out.data_ptr(),
-                                                  m, w.shape[0], k, flags, ws.data_ptr() if ws is not None else None,
-                                                  ws.numel() * 4 if ws is not None else 0, self.stream),
-                      "drt_linear_bf16_ws")
-        return out
+        return linear_ws(self.lib, x, w, None, resid, out, flags, self._ws, self.stream)
 
     def _rms(self, x, g, out):
         _native.check(self.lib.drt_rmsnorm_bf16(x.data_ptr(), x.shape[0], x.shape[1], g.data_ptr(), self.shape.eps,

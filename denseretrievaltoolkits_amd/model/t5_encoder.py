@@ -28,7 +28,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import _native
-from .encoder import HipBertEncoder
+from .encoder import HipBertEncoder, linear_ws, run_on_two_streams
 
 MAX_SEQ = 512
 LIN_RELU = 8     # drt_linear_bf16* flag bit 3
@@ -156,14 +156,7 @@ class HipT5Encoder:
 
     # -- forward --------------------------------------------------------
     def _lin(self, x, w, out, resid=None, flags=0):
-        m, k = x.shape
-        ws = self._ws
-        _native.check(self.lib.drt_linear_bf16_ws(x.data_ptr(), w.data_ptr(), None,
-                                                  resid.data_ptr() if resid is not None else None, out.data_ptr(),
-                                                  m, w.shape[0], k, flags, ws.data_ptr() if ws is not None else None,
-                                                  ws.numel() * 4 if ws is not None else 0, self.stream),
-                      "drt_linear_bf16_ws")
-        return out
+        return linear_ws(self.lib, x, w, None, resid, out, flags, self._ws, self.stream)
 
     def _rms(self, x, g, out):
         _native.check(self.lib.drt_rmsnorm_bf16(x.data_ptr(), x.shape[0], x.shape[1], g.data_ptr(), self.shape.eps,
@@ -194,30 +187,16 @@ class HipT5Encoder:
         mask = attention_mask.to(dev, torch.int64).contiguous() if attention_mask is not None else None
         if (self.split_streams and B >= 2 and B * L >= self.split_min_tokens
                 and not torch.cuda.is_current_stream_capturing()):
-            return self._run_halves(ids, mask)
-        return self._run(ids, mask)
+            # two halves on two streams, as HipBertEncoder (same kernels per half -> same bits)
+            def part(a, b):
+                return lambda out: self._run(ids[a:b], mask[a:b] if mask is not None else None, out=out)
 
-    # Large batches as two independent halves on two HIP streams (HipBertEncoder._run_halves: one
-    # half's memory-bound kernels overlap the other's GEMMs); same kernels per half -> same bits.
-    def _run_halves(self, ids, mask):
-        dev = self.device
-        B, L = ids.shape
-        D = self.shape.d_model
-        out = torch.empty((B * L, D), dtype=torch.bfloat16, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        if self._streams is None:
-            self._streams = [torch.cuda.Stream(dev) for _ in range(2)]
-        self._bias_table(L)             # built on the launch stream, before the halves fork
-        half = B // 2
-        for i, (a, b) in enumerate(((0, half), (half, B))):
-            st = self._streams[i]
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                self._run(ids[a:b], mask[a:b] if mask is not None else None, out=out[a * L:b * L])
-            out.record_stream(st)
-        for st in self._streams:
-            cur.wait_stream(st)
-        return out.view(B, L, D)
+            half = B // 2
+            out = torch.empty((B * L, self.shape.d_model), dtype=torch.bfloat16, device=dev)
+            self._bias_table(L)             # built on the launch stream, before the halves fork
+            return run_on_two_streams(self, out, [(part(0, half), slice(0, half * L)),
+                                                  (part(half, B), slice(half * L, B * L))]).view(B, L, -1)
+        return self._run(ids, mask)
 
     def _run(self, ids, mask, out=None):
         sh = self.shape

@@ -46,13 +46,15 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .. import _native
-from .encoder import BertShape, _check_supported
+from .encoder import BertShape, _check_supported, bert_weights
 from .encoder_bwd import (LIN_GELU, _ptr, attention_backward, attention_forward, attention_varlen_backward,
                           attention_varlen_forward, dropout, grads_out, layernorm_backward, linear, linear_backward,
                           pack_rows, transpose_bf16, unpack_rows)
 
 MAX_TRAIN_SEQ = 512
-MAX_PACKED_TRAIN_LEN = 160   # the whole-sequence attention backward; the streamed one has no varlen form
+# kAbMaxSeq of csrc/drt_common.h: the whole-sequence attention backward (the streamed one has no varlen
+# form).  tests/test_packed_train_host_cpu.py pins it to what the two varlen training entries accept.
+MAX_PACKED_TRAIN_LEN = 160
 
 # Attention launches of the packed tower: False = one launch per batch (forward and backward), True =
 # one per length class of the plan (PackingPlan.classes()).  A/B switch: one launch won in the attention
@@ -81,37 +83,13 @@ class _Weights:
         sd = dict(model.named_parameters())
         self.names = list(sd.keys())
         self.sd = sd
-        self.layers = []
-
-        def b16(t):
-            return t.detach().to(torch.bfloat16).contiguous()
-
-        tr = transpose_bf16   # [N, K] bf16 -> [K, N]
-
-        nl = model.config.num_hidden_layers
-        for i in range(nl):
-            p = f"encoder.layer.{i}."
-            wqkv = b16(torch.cat([sd[p + f"attention.self.{n}.weight"].detach() for n in ("query", "key", "value")]))
-            bqkv = torch.cat([sd[p + f"attention.self.{n}.bias"].detach() for n in ("query", "key", "value")]).float()
-            wo = b16(sd[p + "attention.output.dense.weight"])
-            wi = b16(sd[p + "intermediate.dense.weight"])
-            wf = b16(sd[p + "output.dense.weight"])
-            self.layers.append(dict(
-                wqkv=wqkv, wqkv_t=tr(wqkv), bqkv=bqkv.contiguous(),
-                wo=wo, wo_t=tr(wo), bo=sd[p + "attention.output.dense.bias"].detach().float().contiguous(),
-                g1=sd[p + "attention.output.LayerNorm.weight"].detach().float().contiguous(),
-                b1=sd[p + "attention.output.LayerNorm.bias"].detach().float().contiguous(),
-                wi=wi, wi_t=tr(wi), bi=sd[p + "intermediate.dense.bias"].detach().float().contiguous(),
-                wf=wf, wf_t=tr(wf), bf=sd[p + "output.dense.bias"].detach().float().contiguous(),
-                g2=sd[p + "output.LayerNorm.weight"].detach().float().contiguous(),
-                b2=sd[p + "output.LayerNorm.bias"].detach().float().contiguous(),
-            ))
-        e = "embeddings."
-        self.word = sd[e + "word_embeddings.weight"].detach().float().contiguous()
-        self.pos = sd[e + "position_embeddings.weight"].detach().float().contiguous()
-        self.type = sd[e + "token_type_embeddings.weight"].detach().float().contiguous()
-        self.emb_g = sd[e + "LayerNorm.weight"].detach().float().contiguous()
-        self.emb_b = sd[e + "LayerNorm.bias"].detach().float().contiguous()
+        # the inference encoder's snapshot (model/encoder.py bert_weights) plus each linear's transpose
+        # ([N, K] bf16 -> [K, N], the dgrad GEMM's operand)
+        emb, self.layers = bert_weights(sd, dev, model.config.num_hidden_layers)
+        self.word, self.pos, self.type, self.emb_g, self.emb_b = emb
+        for ly in self.layers:
+            for w in ("wqkv", "wo", "wi", "wf"):
+                ly[w + "_t"] = transpose_bf16(ly[w])
 
 
 def _layernorm(lib, x, g, b, eps, stream):

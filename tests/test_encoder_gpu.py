@@ -294,7 +294,7 @@ def test_gemm_gelu_epilogue_value_sweep(dev):
 
 
 def test_two_stream_halves(dev):
-    """Large batches run as two halves on two streams (HipBertEncoder._run_halves).  At sizes where
+    """Large batches run as two halves on two streams (run_on_two_streams).  At sizes where
     each half's GEMMs take the same kernel as the full batch (256x256 tiles, >= 128 tiles each) the
     result is bit-identical; at small odd sizes the split-K plan differs per M, so only fp rounding
     of the bf16 GEMM outputs differs."""

@@ -56,6 +56,17 @@ def test_attention_entries_accept_empty_inputs():
         assert call(lib, n=0, max_len=161) == native.DRT_EINVAL   # the shape checks come first
 
 
+def test_max_packed_train_len_is_the_bound_both_entries_enforce():
+    """MAX_PACKED_TRAIN_LEN (Python) against kAbMaxSeq (csrc/drt_common.h), through the library's own
+    refusal: the shape checks come before the empty-input return, so n = 0 probes them with no launch."""
+    from denseretrievaltoolkits_amd.model.train_tower import MAX_PACKED_TRAIN_LEN as M
+    lib, native = _lib()
+    assert M == 160
+    for call in (_fwd, _bwd):
+        assert call(lib, n=0, max_len=M, L_pad=M, W=5) == native.DRT_OK
+        assert call(lib, n=0, max_len=M + 1, L_pad=M + 1, W=6) == native.DRT_EINVAL
+
+
 def test_copies_refuse_and_accept():
     lib, native = _lib()
     E, OK = native.DRT_EINVAL, native.DRT_OK

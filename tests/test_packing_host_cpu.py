@@ -40,6 +40,24 @@ def test_plan_length_classes_and_halves():
     assert first.lens == [5, 200, 33]
 
 
+def test_plan_launches():
+    """PackingPlan.launches: what every varlen attention caller iterates over, (seq_ids pointer or None,
+    n_seqs, max_len) per launch."""
+    from denseretrievaltoolkits_amd.model.packing import plan_packing
+    lens, L = [5, 200, 33, 64, 161, 32, 1], 256
+    plan = plan_packing(_prefix_mask(lens, L), L)
+    assert plan.launches(per_class=False) == [(None, 7, 200)]
+    got = plan.launches(per_class=True)
+    classes = plan.classes()
+    assert got == [(ids.data_ptr(), n, ml) for ids, n, ml in classes]
+    # the three classes of test_plan_length_classes_and_halves, each pointer its class tensor's
+    by_ptr = {ids.data_ptr(): sorted(ids.tolist()) for ids, _, _ in classes}
+    assert sorted((by_ptr[p], n, ml) for p, n, ml in got) == sorted(
+        [([0, 5, 6], 3, 32), ([2, 3], 2, 64), ([1, 4], 2, 200)])
+    one = plan_packing(_prefix_mask([3, 30, 17], 32), 32)   # one class: no list either way
+    assert one.launches(per_class=True) == one.launches(per_class=False) == [(None, 3, 30)]
+
+
 @pytest.mark.parametrize("kind", ["holes", "left", "allzero_row", "none", "full"])
 def test_no_plan(kind):
     import torch

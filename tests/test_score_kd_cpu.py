@@ -55,7 +55,10 @@ def _calls(lib, args, ptr, null_at=None, ws_bytes=None):
     def P(count):
         return [None if null_at == i else ptr for i in range(count)]
     q, p, t, S, lse, aux, loss, ws = P(8)
-    fwd = lib.drt_score_kd_fwd(q, p, t, m, n, d, g, T, wce, wkd, 1.0, S, lse, aux, loss, ws, need, None)
+    # null_at = 8 is the backward's workspace: the forward would get eight non-null pointers, pass validation
+    # and, where there is a GPU, launch its kernels on `ptr`, a host address -- so it is not called then
+    fwd = None if null_at == 8 else lib.drt_score_kd_fwd(q, p, t, m, n, d, g, T, wce, wkd, 1.0, S, lse, aux, loss, ws,
+                                                         need, None)
     q, p, t, S, lse, aux, dq, dp = P(8)
     ws = ptr if null_at != 8 else None
     bwd = lib.drt_score_kd_bwd(q, p, t, S, lse, aux, m, n, d, g, T, wce, wkd, None, 1.0, dq, dp, ws, need, None)

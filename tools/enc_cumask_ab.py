@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of CU-masked streams for the encoder's two half-batch streams (HipBertEncoder._run_halves): each
+"""A/B of CU-masked streams for the encoder's two half-batch streams (model/encoder.py run_on_two_streams): each
 half's kernels on its own half of the CUs (hipExtStreamCreateWithCUMask) instead of both halves sharing
 every CU.  Times the passage tower (batch 512 x 128 tokens, BERT-base, random init) per mode, rounds
 alternating.  usage: python tools/enc_cumask_ab.py [--modes none,even,split] [--rounds 3] [--steps 10]"""
