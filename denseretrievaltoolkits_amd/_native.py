@@ -151,6 +151,12 @@ _SIGNATURES = [
                                                         c_vp, c_i32, c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
     ("drt_attention_varlen_backward_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32,
                                                    c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64, c_u64, c_vp]),
+    ("drt_attention_varlen_long_train_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_vp,
+                                                             c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64, c_u64,
+                                                             c_vp]),
+    ("drt_attention_varlen_long_backward_bf16", c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64,
+                                                        c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_u64,
+                                                        c_u64, c_vp]),
     ("drt_pack_rows_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     ("drt_embed_ln_pre_packed", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
                                         c_i32, c_vp, c_vp, c_vp]),

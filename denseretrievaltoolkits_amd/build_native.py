@@ -69,9 +69,13 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 8) -> str:
         if force or _stale(obj, [src] + hdrs):
             todo.append((src, obj))
 
+    # units compiled without the packed FP32 instructions (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32):
+    # pair operations become two scalar ones with the same roundings
+    no_pk_f32 = {"attention_varlen_long.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
     def _compile(so):
         src, obj = so
-        cmd = [hipcc, *flags, "-c", src, "-o", obj]
+        cmd = [hipcc, *flags, *no_pk_f32.get(os.path.basename(src), []), "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         p = subprocess.run(cmd, capture_output=True, text=True)

@@ -21,7 +21,8 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   off in eval mode).  With ``hip_packed_train = True`` (attribute, or
   ``model_args.hip_packed_train``; default off, separate from ``hip_packed``) that tower
   runs on the packed real tokens of the batch (sequences up to 160 tokens, a padding share
-  of at least ``packing.hip_packed_train_min_saving``; otherwise padded, logged once).
+  of at least ``packing.hip_packed_train_min_saving``; otherwise padded, logged once).  Batches whose
+  longest sequence has 161 .. 512 tokens need ``hip_packed_train_long = True`` as well.
   ``encoder_only`` T5 towers stay on the HF module under
   autograd by default; with ``hip_train_t5 = True`` (attribute, or
   ``model_args.hip_train_t5``) a supported T5EncoderModel on the GPU runs the HIP
@@ -95,16 +96,21 @@ def packed_plan(enc, items):
     return plan
 
 
-def packed_train_plan(items, dev):
+def packed_train_plan(items, dev, long=False):
     """The packing plan of a batch for a training pass with ``hip_packed_train`` set, or None (padded
     tower, the reason logged once): the mask is not a batch of non-empty prefixes, or its padding
-    share is below ``packing.hip_packed_train_min_saving``."""
+    share is below ``packing.hip_packed_train_min_saving``.  ``long`` (``hip_packed_train_long``): a batch whose
+    longest sequence is over 160 tokens needs a share of ``packing.hip_packed_train_long_min_saving``."""
     ids = items["input_ids"]
     plan = plan_packing(items.get("attention_mask"), ids.shape[1], device=dev,
                         min_saving=packing.hip_packed_train_min_saving)
     if plan is None or plan.B != ids.shape[0]:
         _log_fallback("hip_packed_train: padded tower, the mask is not a batch of non-empty prefixes with "
                       "enough padding to drop")
+        return None
+    if long and plan.max_len > 160 and \
+            1.0 - plan.T / float(plan.B * plan.L) < packing.hip_packed_train_long_min_saving:
+        _log_fallback("hip_packed_train_long: padded tower, not enough padding to drop at this length")
         return None
     return plan
 
@@ -142,6 +148,9 @@ class DRModel(nn.Module):
         # opt-in: padding-free TRAINING of BERT towers (the autograd pass of train_hidden on the packed
         # rows; model/train_tower.py).  Separate from hip_packed, which covers the no-grad encode only.
         self.hip_packed_train = bool(getattr(model_args, "hip_packed_train", False))
+        # opt-in, with hip_packed_train: batches whose longest sequence has 161 .. 512 tokens train packed too
+        # (the varlen streamed attention pair); without it they keep the padded tower
+        self.hip_packed_train_long = bool(getattr(model_args, "hip_packed_train_long", False))
         self.normalize = normalize
         self.model_args = model_args
         self.train_args = train_args
@@ -301,9 +310,11 @@ class DRModel(nn.Module):
         if why is None and is_t5:
             hidden = train_hidden_t5(model, items["input_ids"], items.get("attention_mask"))
         elif why is None:
-            plan = packed_train_plan(items, next(model.parameters()).device) if self.hip_packed_train else None
+            plan = packed_train_plan(items, next(model.parameters()).device, self.hip_packed_train_long) \
+                if self.hip_packed_train else None
             hidden = train_hidden(model, items["input_ids"], items.get("attention_mask"),
-                                  token_type_ids=items.get("token_type_ids"), plan=plan)
+                                  token_type_ids=items.get("token_type_ids"), plan=plan,
+                                  packed_long=self.hip_packed_train_long)
         else:
             _log_fallback(why)
             out = model(**items, return_dict=True)

@@ -31,9 +31,25 @@ hip_packed_min_saving = 0.10
 # rounded up: 0.15.  DESIGN.md §5 "Padding-free training".
 hip_packed_train_min_saving = 0.15
 
+# The threshold for a batch whose longest sequence is over 160 tokens (hip_packed_train_long).  Measured the same
+# way (tools/packed_train_ab.py --long, profiles/packed_train_long01/packed_train_long_ab.json): packed / padded
+# is 0.897 at a padding share of 0.311 (128 x 256), 0.895 at 0.281 (64 x 512) and 1.061 with no padding and
+# the plan forced -- the plan's device-to-host copy costs 1.3 ms of a 26 ms step, a larger part than of the
+# 41 ms steps above.  The lines from the control cross 1.0 at shares of 0.115 and 0.10; with the same margin
+# of 0.06: 0.18.  DESIGN.md §5 "Padding-free training above 160 tokens".
+hip_packed_train_long_min_saving = 0.18
+
 # Attention length classes: ceil(len / 32) = 1 .. 5 run the kernels that hold the sequence's key
 # blocks in registers, class 0 (len > 160) the streamed form.
 _CLASS_MAX_BLOCKS = 5
+
+# The packed training tower (PackingPlan.split): sequences of at most _SHORT_MAX tokens run the
+# whole-sequence attention pair, longer ones the streamed pair over 128-row tiles.  The long forward's
+# launch classes follow its LDS image (260 B per padded key): up to 192 keys three work-groups share a
+# CU's 160 KiB, up to 288 two, beyond that one.
+_SHORT_MAX = 160
+_TILE_ROWS = 128
+_LONG_CLASS_MAX = (192, 288, 512)
 
 
 @dataclass
@@ -48,6 +64,7 @@ class PackingPlan:
     # for "every sequence", n_seqs, max_len of the class); built on first use
     _classes: Optional[List[Tuple[Optional[torch.Tensor], int, int]]] = field(default=None, repr=False)
     _halves: Optional[list] = field(default=None, repr=False)
+    _split: Optional[dict] = field(default=None, repr=False)
 
     def halves(self):
         """((first sequence, plan) x 2) splitting the batch at the sequence boundary nearest T / 2
@@ -88,11 +105,50 @@ class PackingPlan:
                 self._classes = out
         return self._classes
 
-    def launches(self, per_class: bool):
+    def split(self):
+        """The batch as the packed TRAINING tower differentiates it: a dict, built once, of
+        ``short`` / ``long``: [(seq_ids, n_seqs, max_len)] per attention launch of the sequences of at
+        most / over 160 tokens, keyed by ``per_class`` (False: one launch per part; True: the short ones
+        by length class as ``classes()``, the long ones by the LDS image of the forward: up to
+        ``_LONG_CLASS_MAX`` tokens each); ``tiles``: device int32 [n_tiles, 2] = (sequence, 128-row
+        group) of every group of a long sequence that holds a token, a sequence's groups adjacent;
+        ``n_tiles``."""
+        if self._split is None:
+            dev = self.cu_seqlens.device
+            short = [b for b, n in enumerate(self.lens) if n <= _SHORT_MAX]
+            long_ = [b for b, n in enumerate(self.lens) if n > _SHORT_MAX]
+            tiles = [(b, g) for b in long_ for g in range((self.lens[b] + _TILE_ROWS - 1) // _TILE_ROWS)]
+
+            def part(ids, class_of):
+                if not ids:
+                    return {False: [], True: []}
+                groups = {}
+                for b in ids:
+                    groups.setdefault(class_of(self.lens[b]), []).append(b)
+                order = sorted(groups, reverse=True)                          # longest first
+                flat = torch.tensor([b for c in order for b in groups[c]], dtype=torch.int32).to(dev)
+                whole = None if len(ids) == self.B else flat                 # every sequence: no list
+                out, at = [], 0
+                for c in order:
+                    n = len(groups[c])
+                    out.append((flat[at:at + n] if len(order) > 1 or whole is not None else None, n,
+                                max(self.lens[b] for b in groups[c])))
+                    at += n
+                return {False: [(whole, len(ids), max(self.lens[b] for b in ids))], True: out}
+
+            self._split = {
+                "short": part(short, lambda n: (n + 31) // 32),
+                "long": part(long_, lambda n: next(i for i, m in enumerate(_LONG_CLASS_MAX) if n <= m)),
+                "tiles": torch.tensor(tiles, dtype=torch.int32).reshape(-1, 2).to(dev), "n_tiles": len(tiles)}
+        return self._split
+
+    def launches(self, per_class: bool, part: Optional[str] = None):
         """The (seq_ids pointer or None, n_seqs, max_len) of each varlen attention launch over the batch,
         forward or backward: one per length class (``classes()``), or one for the whole batch.  Callers
-        build it once per pass, outside their layer loop."""
-        launches = self.classes() if per_class else [(None, self.B, self.max_len)]
+        build it once per pass, outside their layer loop.  ``part`` = "short" / "long": the launches of
+        that part of ``split()`` instead."""
+        launches = self.split()[part][bool(per_class)] if part else \
+            self.classes() if per_class else [(None, self.B, self.max_len)]
         return [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]
 
 

@@ -79,6 +79,8 @@ class RRModel(nn.Module):
         self.hip_packed = bool(getattr(model_args, "hip_packed", False))
         # opt-in: padding-free training of a BERT pair tower (model/train_tower.py); separate from hip_packed
         self.hip_packed_train = bool(getattr(model_args, "hip_packed_train", False))
+        # opt-in, with hip_packed_train: pairs of 161 .. 512 tokens train packed too (default: padded tower)
+        self.hip_packed_train_long = bool(getattr(model_args, "hip_packed_train_long", False))
         if train_args is not None:
             self.loss_fn_str = train_args.loss_fn
             self.margin = train_args.margin
@@ -174,9 +176,10 @@ class RRModel(nn.Module):
             plan = None
             if self.hip_packed_train:
                 from .biencoder import packed_train_plan
-                plan = packed_train_plan(items, dev)
+                plan = packed_train_plan(items, dev, self.hip_packed_train_long)
             hidden = train_hidden(self.lm, items["input_ids"], items.get("attention_mask"),
-                                  token_type_ids=items.get("token_type_ids"), plan=plan)
+                                  token_type_ids=items.get("token_type_ids"), plan=plan,
+                                  packed_long=self.hip_packed_train_long)
         else:
             from .biencoder import _log_fallback
             why = "tower on the CPU" if dev.type != "cuda" else tower_supported(self.lm) or "feature / length"

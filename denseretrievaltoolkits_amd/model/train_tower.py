@@ -36,8 +36,11 @@ never touch it), ``pack_rows`` zeroes the tail of the incoming gradient, and the
 dropout and dgrad of a zero gradient row are zero.  Hidden-site dropout uses the existing kernels and
 GEMM epilogues unchanged, so element (t, j) of a packed matrix draws index ``t * H + j``: the same
 distribution as the padded run, different draws; the attention keeps of every real (query, key) ARE
-the padded run's (the hash takes the padded row).  A plan with ``max_len > 160`` (the streamed
-backward has no varlen form) keeps the padded tower, logged once.
+the padded run's (the hash takes the padded row).  A plan with ``max_len > 160`` keeps the padded
+tower, logged once, unless ``hip_packed_train_long`` is set as well (``train_hidden(..., packed_long=True)``):
+then the sequences over 160 tokens, up to 512, run the varlen forms of the streamed attention pair
+(``drt_attention_varlen_long_train_forward_bf16`` / ``..._long_backward_bf16`` over the plan's tile table) and
+the shorter ones of the same batch the whole-sequence pair.
 """
 from __future__ import annotations
 
@@ -55,12 +58,17 @@ MAX_TRAIN_SEQ = 512
 # kAbMaxSeq of csrc/drt_common.h: the whole-sequence attention backward (the streamed one has no varlen
 # form).  tests/test_packed_train_host_cpu.py pins it to what the two varlen training entries accept.
 MAX_PACKED_TRAIN_LEN = 160
+# kAblMaxSeq: the streamed pair's varlen forms, behind hip_packed_train_long
+# (tests/test_packed_train_long_host_cpu.py pins it to what the two long entries accept).
+MAX_PACKED_TRAIN_LONG_LEN = 512
 
 # Attention launches of the packed tower: False = one launch per batch (forward and backward), True =
 # one per length class of the plan (PackingPlan.classes()).  A/B switch: one launch won in the attention
 # backward alone (one layer at 512 x 128 with lengths 32-128: 182 us in one launch, 205 us in 4, 238 us
 # padded; at 256 x 160: 178 / 186 / 215) and end to end (31.56 against 31.84 ms, 25.06 against 25.29 ms);
-# DESIGN.md §5 "Padding-free training" (tools/packed_train_ab.py, profiles/packed_train01/).
+# DESIGN.md §5 "Padding-free training" (tools/packed_train_ab.py, profiles/packed_train01/).  With
+# hip_packed_train_long the switch also groups the long sequences' forward launches by LDS image
+# (PackingPlan.split()); the streamed backward is one launch pair either way.
 packed_train_classes = False
 
 
@@ -113,6 +121,8 @@ class _Step:
         self.types = types   # token_type_ids [B, L] int64 or None (all type 0)
         self.B, self.L = ids.shape
         self.plan = plan     # PackingPlan: the tower runs on ``rows`` packed rows, of which plan.T are tokens
+        # a sequence over MAX_PACKED_TRAIN_LEN tokens: the attention pair routes by plan.split()
+        self.long = plan is not None and plan.max_len > MAX_PACKED_TRAIN_LEN
         self.rows = (plan.T + 31) // 32 * 32 if plan is not None else self.B * self.L
         self.H, self.heads, self.eps = cfg.hidden_size, cfg.num_attention_heads, float(cfg.layer_norm_eps)
         self.scale = 1.0 / (self.H // self.heads) ** 0.5
@@ -183,7 +193,7 @@ def layer_forward(st: _Step, i: int, h):
     qkv = linear(h, ly["wqkv"], torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev), bias=ly["bqkv"])
     if st.plan is not None:
         ctx, lse, bits = attention_varlen_forward(qkv, st.plan, heads, st.scale, drop=(pa, seed, s_att),
-                                                  per_class=packed_train_classes)
+                                                  per_class=packed_train_classes, long=st.long)
     else:
         ctx, lse, bits = attention_forward(qkv, st.mask, B, L, heads, st.scale, drop=(pa, seed, s_att))
     # x1 = dropout(ctx Wo^T + bo) + h, dropout in the GEMM epilogue
@@ -228,7 +238,7 @@ def layer_backward(st: _Step, i: int, saved, d) -> Tuple[torch.Tensor, Dict[str,
     # gradients without a pass over dQKV
     if st.plan is not None:
         dqkv, dbqkv = attention_varlen_backward(qkv, ctx, dctx, lse, bits, st.plan, heads, st.scale,
-                                                drop=(pa, seed, s_att), per_class=packed_train_classes)
+                                                drop=(pa, seed, s_att), per_class=packed_train_classes, long=st.long)
     else:
         dqkv, dbqkv = attention_backward(qkv, ctx, dctx, lse, st.mask, bits, st.B, st.L, heads, st.scale,
                                          drop=(pa, seed, s_att), want_dbias=True)
@@ -311,18 +321,19 @@ def _param_groups(model):
 
 
 def train_hidden(model, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                 seed: Optional[int] = None, token_type_ids: Optional[torch.Tensor] = None, plan=None) -> torch.Tensor:
+                 seed: Optional[int] = None, token_type_ids: Optional[torch.Tensor] = None, plan=None,
+                 packed_long: bool = False) -> torch.Tensor:
     """last_hidden_state fp32 [B, L, H] of ``model`` with the HIP tower backward attached (one autograd
     node per layer).  Dropout follows ``model.training`` and the config's probabilities (seed: torch
     CPU RNG).  ``plan`` (model/packing.py PackingPlan of this batch's mask): the tower runs on the
     packed rows and the pad positions of the result are zeros; a plan the packed tower cannot take
-    (its longest sequence over 160 tokens, or a plan of another batch shape) keeps the padded tower,
-    logged once."""
+    (its longest sequence over 160 tokens -- over 512 with ``packed_long``, the ``hip_packed_train_long``
+    flag -- or a plan of another batch shape) keeps the padded tower, logged once."""
     why = tower_supported(model)
     if why is not None:
         raise NotImplementedError(f"HIP training tower: {why}")
     if plan is not None:
-        if plan.max_len > MAX_PACKED_TRAIN_LEN:
+        if plan.max_len > (MAX_PACKED_TRAIN_LONG_LEN if packed_long else MAX_PACKED_TRAIN_LEN):
             _log_fallback(f"hip_packed_train: padded tower, longest sequence {plan.max_len} > {MAX_PACKED_TRAIN_LEN}")
             plan = None
         elif (plan.B, plan.L) != tuple(input_ids.shape):

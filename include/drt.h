@@ -617,7 +617,8 @@ int drt_unpack_rows_bf16(const void* packed, const int32_t* cu_seqlens, int64_t 
                          void* out, void* stream);
 /* ------------------------------------------------------------------------
  * Padding-free BERT training: the attention pair and the copies of a tower that runs on the packed
- * [T, H] rows (model/train_tower.py).  Whole-sequence kernels only: 1 <= max_len <= 160.  A bad
+ * [T, H] rows (model/train_tower.py).  The first pair runs the whole-sequence kernels only:
+ * 1 <= max_len <= 160; the "long" pair below reaches 512.  A bad
  * argument (max_len outside that range, head_dim != 64, drop_p outside [0, 1)) is DRT_EINVAL before
  * any HIP call; n_seqs == 0 or T == 0 is DRT_OK.
  * Layouts, with T = cu[B] and W = ceil(longest sequence of the BATCH / 32), the same for every launch
@@ -640,6 +641,24 @@ int drt_unpack_rows_bf16(const void* packed, const int32_t* cu_seqlens, int64_t 
  *   column sums of sequence b's dqkv rows as stored; drt_colsum_f32 over the B rows, after the last
  *   launch of a batch, is the q / k / v bias gradient in a fixed order.  A sequence run alone with
  *   max_len = len has the dqkv bits of drt_attention_backward_bf16 (B = 1, L = len, no mask).
+ * Sequences of 161 .. 512 tokens (streamed kernels; the two entries above keep refusing max_len > 160):
+ * drt_attention_varlen_long_train_forward_bf16: the training forward with 1 <= max_len <= 512, same
+ *   arguments, layouts, keeps and refusals; above 160 each wave loops over the query blocks of its own
+ *   sequence and the launch's LDS image is sized by max_len (about 134 KB at 512).  At drop_p = 0 the
+ *   ctx bits of drt_attention_varlen_forward_bf16.  Only the words that hold a key of the sequence
+ *   (the first ceil(len / 32) of a query) are written above 160.
+ * drt_attention_varlen_long_backward_bf16: dqkv of the sequences named by `tiles`, int32 [n_tiles][2]
+ *   = (sequence, 128-row group), one entry for every group of a sequence that holds a token, a
+ *   sequence's entries adjacent (NULL with n_tiles > 0 is refused).  One work-group per (tile, head):
+ *   the dK / dV rows of the tile's keys and the dQ rows of its queries, streamed over the blocks of
+ *   that sequence alone.  1 <= max_len <= 512; a length over max_len is clamped (rows past it are not
+ *   touched), a tile whose group starts at or past the length, and an empty sequence, write nothing.
+ *   drop_bits == NULL draws the same keeps again.  dsum (may be NULL): fp32 [n_tiles][3H], row t the
+ *   column sums of tile t's stored rows (dQ of its queries, dK and dV of its keys); drt_colsum_f32
+ *   over the rows -- together with the short sequences' rows of drt_attention_varlen_backward_bf16 --
+ *   is the bias gradient, in a fixed order and bit-equal between runs (no atomics).  A sequence alone
+ *   (max_len = len) has the dqkv bits of drt_attention_backward_bf16 (B = 1, L = len, no mask) on the
+ *   same lse and keep bits, at any len <= 512 above 160; below, within the same bounds.
  * drt_pack_rows_bf16: out [out_rows, H] bf16 = the real rows of padded [B * L, H] in packed order
  *   (the inverse of drt_unpack_rows_bf16, and its backward), rows cu[B] .. out_rows - 1 zeroed.
  *   H % 8 == 0, padded and out 16-byte aligned.
@@ -656,6 +675,17 @@ int drt_attention_varlen_backward_bf16(const void* qkv, const void* ctx, const v
                                        const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads,
                                        int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
                                        void* stream);
+int drt_attention_varlen_long_train_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                                 int64_t n_seqs, int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                                 void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
+                                                 int32_t head_dim, float scale, float drop_p, uint64_t seed,
+                                                 uint64_t site, void* stream);
+int drt_attention_varlen_long_backward_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse,
+                                            const int32_t* cu_seqlens, const int32_t* tiles, int64_t n_tiles,
+                                            int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                            const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads,
+                                            int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
+                                            void* stream);
 int drt_pack_rows_bf16(const void* padded, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H, void* out,
                        int64_t out_rows, void* stream);
 int drt_embed_ln_pre_packed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, int64_t B,

@@ -37,6 +37,13 @@ SHAPES = [
     ("256x160_len60-160", 256, 160, 60, 160),
     ("512x128_full_control", 512, 128, 128, 128),
 ]
+# --long: batches whose longest sequence is over 160 tokens (hip_packed_train_long: the streamed varlen
+# attention pair); the attention timings then compare it with the padded streamed pair
+LONG_SHAPES = [
+    ("128x256_len100-256", 128, 256, 100, 256),
+    ("64x512_len200-512", 64, 512, 200, 512),
+    ("128x256_full_control", 128, 256, 256, 256),
+]
 
 
 def _time(fn, steps, warmup=2):
@@ -57,6 +64,7 @@ def main():
     ap.add_argument("--out", default=os.path.join("profiles", "packed_train01", "packed_train_ab.json"))
     ap.add_argument("--pkg-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--padded-only", action="store_true")
+    ap.add_argument("--long", action="store_true", help="the shapes over 160 tokens, packed with packed_long")
     args = ap.parse_args()
     sys.path.insert(0, args.pkg_root)
     from transformers import BertConfig, BertModel
@@ -72,7 +80,8 @@ def main():
     lib = _native.load()
     rec = {"tool": "tools/packed_train_ab.py", "steps": args.steps, "rounds": args.rounds,
            "pkg_root": os.path.relpath(args.pkg_root), "device": torch.cuda.get_device_name(0), "shapes": {}}
-    for name, B, L, lo, hi in SHAPES:
+    long = {"long": True} if args.long else {}
+    for name, B, L, lo, hi in (LONG_SHAPES if args.long else SHAPES):
         g = torch.Generator().manual_seed(B * 1000 + L)
         lens = torch.randint(lo, hi + 1, (B,), generator=g)
         mask = (torch.arange(L)[None, :] < lens[:, None]).to(torch.int64).to(dev)
@@ -96,7 +105,7 @@ def main():
                     keep = train_tower.packed_train_classes
                     train_tower.packed_train_classes = classes
                     try:
-                        return step(plan=plan_packing(mask, L, force=force))
+                        return step(plan=plan_packing(mask, L, force=force), packed_long=args.long)
                     finally:
                         train_tower.packed_train_classes = keep
                 return run
@@ -108,7 +117,7 @@ def main():
                 return step()
 
             variants.update(packed_one_launch=packed(False), packed_classes=packed(True),
-                            padded_plus_plan=padded_plus_plan, packed_ready_plan=lambda: step(plan=ready))
+                            padded_plus_plan=padded_plus_plan, packed_ready_plan=lambda: step(plan=ready, packed_long=args.long))
         times = {k: [] for k in variants}
         for _ in range(args.rounds):
             for k, fn in variants.items():
@@ -130,7 +139,7 @@ def main():
             qkv_t, dctx_t = qkv_p[sel].contiguous(), dctx_p[sel].contiguous()
             drop = (0.1, 1234, 1)
             ctx_p, lse_p, bits_p = encoder_bwd.attention_forward(qkv_p, mask, B, L, heads, 0.125, drop=drop)
-            ctx_t, lse_t, bits_t = encoder_bwd.attention_varlen_forward(qkv_t, plan, heads, 0.125, drop=drop)
+            ctx_t, lse_t, bits_t = encoder_bwd.attention_varlen_forward(qkv_t, plan, heads, 0.125, drop=drop, **long)
 
             def bwd_padded():
                 encoder_bwd.attention_backward(qkv_p, ctx_p, dctx_p, lse_p, mask, bits_p, B, L, heads, 0.125, drop=drop,
@@ -138,11 +147,11 @@ def main():
 
             def bwd_varlen(classes):
                 return lambda: encoder_bwd.attention_varlen_backward(qkv_t, ctx_t, dctx_t, lse_t, bits_t, plan, heads,
-                                                                      0.125, drop=drop, per_class=classes)
+                                                                      0.125, drop=drop, per_class=classes, **long)
 
             def fwd_varlen(classes):
                 return lambda: encoder_bwd.attention_varlen_forward(qkv_t, plan, heads, 0.125, drop=drop,
-                                                                     per_class=classes)
+                                                                     per_class=classes, **long)
 
             attn = {"bwd_padded": bwd_padded, "bwd_varlen_one_launch": bwd_varlen(False),
                     "bwd_varlen_classes": bwd_varlen(True),
@@ -153,7 +162,7 @@ def main():
                 for k, fn in attn.items():
                     at[k].append(_time(fn, 100, warmup=10))
             out["attention_ms"] = at
-            out["attention_launches_with_classes"] = len(plan.classes())
+            out["attention_launches_with_classes"] = len(plan.launches(True, "long")) if args.long else len(plan.classes())
             del qkv_p, dctx_p, qkv_t, dctx_t, ctx_p, lse_p, bits_p, ctx_t, lse_t, bits_t
         rec["shapes"][name] = out
         print(name, json.dumps(out), flush=True)
