@@ -593,15 +593,39 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_long_dq_kernel(AttnBwdAr
   }
 }
 
-// Launch of the streamed pair's VL kernels over a tile table: one work-group per (tile, head), tile
-// major, the dK / dV kernel (`pick(0)`) then the dQ kernel (`pick(1)`); static LDS only.
+// Launch of the streamed pair over `grid` -- (sequence, head) x 128-row group, or one work-group per
+// (tile, head) of a tile table (VL): the dK / dV kernel (`pick(0)`) then the dQ kernel (`pick(1)`);
+// static LDS only.
 template <typename Pick>
-static int launch_attention_bwd_long_vl(Pick&& pick, AttnBwdArgs& a, int64_t n_tiles, hipStream_t stream) {
+static int launch_attention_bwd_long(Pick&& pick, AttnBwdArgs& a, dim3 grid, hipStream_t stream) {
   void* args[] = {&a};
-  const dim3 grid((unsigned)(n_tiles * a.heads));
   hipLaunchKernel((const void*)pick(0), grid, dim3(256), args, 0, stream);
   hipLaunchKernel((const void*)pick(1), grid, dim3(256), args, 0, stream);
   return hip_status(hipGetLastError());
+}
+
+// The checked arguments of the two varlen backwards (drt_attention_varlen_backward_bf16 and its _long_
+// form, which differ in `max_seq` and in what `ids` lists: n sequences, or with `tiled` the n rows of a
+// tile table, which is then required), in the order the contract (drt.h) states: shapes and drop_p,
+// then DRT_OK with *launch = false for an empty input, then pointers, L_pad and W.
+inline int varlen_train_bwd_args(AttnBwdArgs& a, bool* launch, int max_seq, bool tiled, const void* qkv,
+                                 const void* ctx, const void* dctx, const float* lse, const int32_t* cu_seqlens,
+                                 const int32_t* ids, int64_t n, int32_t max_len, int64_t L_pad, int64_t T, int32_t W,
+                                 const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads, int32_t head_dim,
+                                 float scale, float drop_p, uint64_t seed, uint64_t site) {
+  *launch = false;
+  DRT_REQUIRE(n >= 0 && T >= 0 && max_len >= 1 && max_len <= max_seq && heads > 0 && head_dim == 64);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  DRT_REQUIRE(n * heads < (1ll << 31) && T < (1ll << 31));
+  if (n == 0 || T == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && ctx && dctx && lse && cu_seqlens && (ids || !tiled) && dqkv && L_pad >= max_len);
+  const bool drop = drop_p > 0.0f;
+  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
+  a = AttnBwdArgs{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, nullptr, (__bf16*)dqkv, 0, 0,
+                  heads, heads * 64, scale, drop_p, seed, site, drop ? drop_bits : nullptr, dsum, nullptr, nullptr,
+                  cu_seqlens, tiled ? nullptr : ids, max_len, L_pad, T, W, tiled ? ids : nullptr};
+  *launch = true;
+  return DRT_OK;
 }
 
 }  // namespace drt

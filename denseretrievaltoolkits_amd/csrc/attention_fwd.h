@@ -390,4 +390,25 @@ static int launch_attention_fwd(Pick&& pick, AttnArgs& a, int len, bool rb, int6
   return hip_status(hipGetLastError());
 }
 
+// The checked arguments of the two varlen training forwards (drt_attention_varlen_train_forward_bf16 and
+// its _long_ form, which differ in `max_seq`), in the order the contract (drt.h) states: shapes and
+// drop_p, then DRT_OK with *launch = false for an empty input, then pointers, L_pad and W.
+inline int varlen_train_fwd_args(AttnArgs& a, bool* launch, int max_seq, const void* qkv, const int32_t* cu_seqlens,
+                                 const int32_t* seq_ids, int64_t n_seqs, int32_t max_len, int64_t L_pad, int64_t T,
+                                 int32_t W, void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
+                                 int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site) {
+  *launch = false;
+  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= max_seq && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
+  DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
+  if (n_seqs == 0 || T == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && cu_seqlens && ctx && L_pad >= max_len);
+  const bool drop = drop_p > 0.0f;
+  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
+  a = AttnArgs{(const __bf16*)qkv, nullptr, (__bf16*)ctx, 0, 0, heads, heads * head_dim, scale, lse, drop_p, seed, site,
+               drop ? drop_bits : nullptr, nullptr, cu_seqlens, seq_ids, max_len, L_pad, T, W};
+  *launch = true;
+  return DRT_OK;
+}
+
 }  // namespace drt

@@ -21,18 +21,15 @@ int drt_attention_varlen_long_train_forward_bf16(const void* qkv, const int32_t*
                                                  void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
                                                  int32_t head_dim, float scale, float drop_p, uint64_t seed,
                                                  uint64_t site, void* stream) {
-  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
-  if (max_len <= kAbMaxSeq)
+  if (max_len <= kAbMaxSeq)   // every check is that entry's own, at its tighter bound
     return drt_attention_varlen_train_forward_bf16(qkv, cu_seqlens, seq_ids, n_seqs, max_len, L_pad, T, W, ctx, lse,
                                                    drop_bits, heads, head_dim, scale, drop_p, seed, site, stream);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
-  if (n_seqs == 0 || T == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && cu_seqlens && ctx && L_pad >= max_len);
+  AttnArgs a;
+  bool launch;
+  const int rc = varlen_train_fwd_args(a, &launch, kMaxSeq, qkv, cu_seqlens, seq_ids, n_seqs, max_len, L_pad, T, W, ctx,
+                                       lse, drop_bits, heads, head_dim, scale, drop_p, seed, site);
+  if (!launch) return rc;
   const bool drop = drop_p > 0.0f;
-  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
-  AttnArgs a{(const __bf16*)qkv, nullptr, (__bf16*)ctx, 0, 0, heads, heads * head_dim, scale, lse, drop_p, seed, site,
-             drop ? drop_bits : nullptr, nullptr, cu_seqlens, seq_ids, max_len, L_pad, T, W};
   using Kernel = void (*)(AttnArgs);
   static constexpr Kernel kernels[2] = {attention_fwd_kernel<0, false, false, 2>,   // [drop]; NB = 0
                                         attention_fwd_kernel<0, true, false, 2>};
@@ -49,22 +46,20 @@ int drt_attention_varlen_long_backward_bf16(const void* qkv, const void* ctx, co
                                             const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads,
                                             int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
                                             void* stream) {
-  DRT_REQUIRE(n_tiles >= 0 && T >= 0 && max_len >= 1 && max_len <= kAblMaxSeq && heads > 0 && head_dim == 64);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  DRT_REQUIRE(n_tiles * heads < (1ll << 31) && T < (1ll << 31));
-  if (n_tiles == 0 || T == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx && dctx && lse && cu_seqlens && tiles && dqkv && L_pad >= max_len);
+  AttnBwdArgs a;
+  bool launch;
+  const int rc = varlen_train_bwd_args(a, &launch, kAblMaxSeq, true, qkv, ctx, dctx, lse, cu_seqlens, tiles, n_tiles,
+                                       max_len, L_pad, T, W, drop_bits, dqkv, dsum, heads, head_dim, scale, drop_p, seed,
+                                       site);
+  if (!launch) return rc;
   const bool drop = drop_p > 0.0f;
-  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
-  AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, nullptr, (__bf16*)dqkv, 0, 0,
-                heads, heads * 64, scale, drop_p, seed, site, drop ? drop_bits : nullptr, dsum, nullptr, nullptr,
-                cu_seqlens, nullptr, max_len, L_pad, T, W, tiles};
   using Kernel = void (*)(AttnBwdArgs);
   // [dkdv, dq][drop]
   static constexpr Kernel vl[2][2] = {
       {attention_bwd_long_dkdv_kernel<false, false, true>, attention_bwd_long_dkdv_kernel<true, false, true>},
       {attention_bwd_long_dq_kernel<false, false, true>, attention_bwd_long_dq_kernel<true, false, true>}};
-  return launch_attention_bwd_long_vl([&](int k) { return vl[k][drop]; }, a, n_tiles, (hipStream_t)stream);
+  return launch_attention_bwd_long([&](int k) { return vl[k][drop]; }, a, dim3((unsigned)(n_tiles * heads)),
+                                   (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -377,15 +377,12 @@ int drt_attention_varlen_train_forward_bf16(const void* qkv, const int32_t* cu_s
                                             void* ctx, float* lse, uint32_t* drop_bits, int32_t heads,
                                             int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
                                             void* stream) {
-  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kAbMaxSeq && heads > 0 && head_dim == kHeadDim);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
-  if (n_seqs == 0 || T == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && cu_seqlens && ctx && L_pad >= max_len);
+  AttnArgs a;
+  bool launch;
+  const int rc = varlen_train_fwd_args(a, &launch, kAbMaxSeq, qkv, cu_seqlens, seq_ids, n_seqs, max_len, L_pad, T, W,
+                                       ctx, lse, drop_bits, heads, head_dim, scale, drop_p, seed, site);
+  if (!launch) return rc;
   const bool drop = drop_p > 0.0f;
-  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
-  AttnArgs a{(const __bf16*)qkv, nullptr, (__bf16*)ctx, 0, 0, heads, heads * head_dim, scale, lse, drop_p, seed, site,
-             drop ? drop_bits : nullptr, nullptr, cu_seqlens, seq_ids, max_len, L_pad, T, W};
   using Kernel = void (*)(AttnArgs);
   static constexpr Kernel kernels[5][2] = {
       {attention_fwd_kernel<1, false, false, 2>, attention_fwd_kernel<1, true, false, 2>},

@@ -948,11 +948,8 @@ int drt_attention_backward_bf16(const void* qkv, const void* ctx, const void* dc
   int rc;
   if (L > kAbMaxSeq) {   // streamed kernels: dK / dV over key groups, dQ over query groups
     DRT_REQUIRE(!drop || drop_bits);   // the forward's keep bits
-    void* args[] = {&a};
-    const dim3 grid((unsigned)(B * heads), (unsigned)((L + kAblGroup - 1) / kAblGroup));
-    hipLaunchKernel((const void*)long_dkdv[drop][rb], grid, dim3(256), args, 0, st);
-    hipLaunchKernel((const void*)long_dq[drop][rb], grid, dim3(256), args, 0, st);
-    rc = hip_status(hipGetLastError());
+    rc = launch_attention_bwd_long([&](int k) { return (k ? long_dq : long_dkdv)[drop][rb]; }, a,
+                                   dim3((unsigned)(B * heads), (unsigned)((L + kAblGroup - 1) / kAblGroup)), st);
   } else {
     rc = launch_attention_bwd_rk([&](int nb) { return rk[nb - 1][drop][rb]; }, a, (int)L, drop, rb, B * heads, st);
   }
@@ -976,16 +973,13 @@ int drt_attention_varlen_backward_bf16(const void* qkv, const void* ctx, const v
                                        const uint32_t* drop_bits, void* dqkv, float* dsum, int32_t heads,
                                        int32_t head_dim, float scale, float drop_p, uint64_t seed, uint64_t site,
                                        void* stream) {
-  DRT_REQUIRE(n_seqs >= 0 && T >= 0 && max_len >= 1 && max_len <= kAbMaxSeq && heads > 0 && head_dim == 64);
-  DRT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f);
-  DRT_REQUIRE(n_seqs * heads < (1ll << 31) && T < (1ll << 31));
-  if (n_seqs == 0 || T == 0) return DRT_OK;
-  DRT_REQUIRE(qkv && ctx && dctx && lse && cu_seqlens && dqkv && L_pad >= max_len);
+  AttnBwdArgs a;
+  bool launch;
+  const int rc = varlen_train_bwd_args(a, &launch, kAbMaxSeq, false, qkv, ctx, dctx, lse, cu_seqlens, seq_ids, n_seqs,
+                                       max_len, L_pad, T, W, drop_bits, dqkv, dsum, heads, head_dim, scale, drop_p, seed,
+                                       site);
+  if (!launch) return rc;
   const bool drop = drop_p > 0.0f;
-  DRT_REQUIRE(!(drop && drop_bits) || W * 32 >= max_len);
-  AttnBwdArgs a{(const __bf16*)qkv, (const __bf16*)ctx, (const __bf16*)dctx, lse, nullptr, (__bf16*)dqkv, 0, 0,
-                heads, heads * 64, scale, drop_p, seed, site, drop ? drop_bits : nullptr, dsum, nullptr, nullptr,
-                cu_seqlens, seq_ids, max_len, L_pad, T, W};
   using Kernel = void (*)(AttnBwdArgs);
 #define DRT_AB_VL(NB) {attention_bwd_rk_kernel<NB, false, false, true>, attention_bwd_rk_kernel<NB, true, false, true>}
   static constexpr Kernel vl[5][2] = {DRT_AB_VL(1), DRT_AB_VL(2), DRT_AB_VL(3), DRT_AB_VL(4), DRT_AB_VL(5)};

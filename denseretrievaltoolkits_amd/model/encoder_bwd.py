@@ -13,7 +13,10 @@ kernels for the bf16 activations the HIP forward stores:
                         (include/drt.h);
 * ``linear`` / ``dropout`` / ``attention_forward`` / ``attention_backward``: the forward GEMM with
                         its training epilogues, the hashed dropout, and the attention pair with
-                        its optional relative-position bias, dropout and bias / table gradients.
+                        its optional relative-position bias, dropout and bias / table gradients;
+* ``attention_varlen_forward`` / ``attention_varlen_backward``: the same pair over a packed batch,
+                        routed by ``PackingPlan.split()`` alone: sequences over 160 tokens through
+                        the streamed entries, the others through the whole-sequence ones.
 """
 from __future__ import annotations
 
@@ -116,13 +119,13 @@ def attention_backward(qkv, ctx, dctx, lse, mask, bits, B, L, heads, scale, relb
     return dqkv, extra
 
 
-def attention_varlen_forward(qkv, plan, heads, scale, drop=None, per_class=False, long=False):
+def attention_varlen_forward(qkv, plan, heads, scale, drop=None, per_class=False):
     """(ctx bf16 [rows, heads*64], lse fp32 [heads, T], keep bits [heads, T, W] or None) of the attention
     over the packed ``qkv`` [rows >= T, 3 heads*64] of ``plan`` (model/packing.py); rows past T of ctx
     are zeros.  ``drop`` = (p, seed, site): the keeps of every real (query, key) are those of
-    ``attention_forward`` on the padded batch [B, plan.L].  ``long`` (a plan whose longest sequence has
-    161 .. 512 tokens): the sequences of at most 160 tokens through the same entry, the longer ones
-    through ``drt_attention_varlen_long_train_forward_bf16`` (``plan.split()``)."""
+    ``attention_forward`` on the padded batch [B, plan.L].  The launches are those of ``plan.split()``:
+    the sequences over 160 tokens through ``drt_attention_varlen_long_train_forward_bf16``, the others
+    through ``drt_attention_varlen_train_forward_bf16``; an empty part issues no call."""
     dev = qkv.device
     lib = _native.load()
     rows, T = qkv.shape[0], plan.T
@@ -134,23 +137,22 @@ def attention_varlen_forward(qkv, plan, heads, scale, drop=None, per_class=False
     W = (plan.max_len + 31) // 32
     bits = torch.empty((heads, T, W), dtype=torch.int32, device=dev) if p > 0 else None
     s = _native.stream_ptr(dev)
-    parts = [(lib.drt_attention_varlen_train_forward_bf16, plan.launches(per_class, "short" if long else None))]
-    if long:   # longest first: the work-groups that hold a CU alone start before the short ones fill it
-        parts.insert(0, (lib.drt_attention_varlen_long_train_forward_bf16, plan.launches(per_class, "long")))
-    for entry, launches in parts:
-        for sp, n, ml in launches:
+    # longest first: the work-groups that hold a CU alone start before the short ones fill it
+    for entry, part in ((lib.drt_attention_varlen_long_train_forward_bf16, "long"),
+                        (lib.drt_attention_varlen_train_forward_bf16, "short")):
+        for sp, n, ml in plan.launches(per_class, part):
             _native.check(entry(qkv.data_ptr(), plan.cu_seqlens.data_ptr(), sp, n, ml, plan.L, T, W, ctx.data_ptr(),
                                 lse.data_ptr(), _ptr(bits), heads, 64, float(scale), float(p), seed, site, s),
                           "varlen attention training forward")
     return ctx, lse, bits
 
 
-def attention_varlen_backward(qkv, ctx, dctx, lse, bits, plan, heads, scale, drop=None, per_class=False, long=False):
+def attention_varlen_backward(qkv, ctx, dctx, lse, bits, plan, heads, scale, drop=None, per_class=False):
     """(dqkv bf16 like qkv with zero rows past T, dbias fp32 [3 * heads * 64]) of
-    ``attention_varlen_forward``.  Every launch leaves its sequences' column sums in one [B, 3H]
-    matrix; one fixed-order column sum after the last launch finishes dbias.  ``long``: the sequences
-    over 160 tokens through ``drt_attention_varlen_long_backward_bf16`` over the plan's tile table, whose
-    per-tile sums are the matrix's rows B .. B + n_tiles - 1 (the long sequences' own rows stay zero)."""
+    ``attention_varlen_forward``.  Every launch leaves its sequences' column sums in one [B + n_tiles, 3H]
+    matrix; one fixed-order column sum after the last launch finishes dbias.  The sequences over 160
+    tokens run ``drt_attention_varlen_long_backward_bf16`` over the plan's tile table, whose per-tile sums
+    are the matrix's rows B .. B + n_tiles - 1 (the long sequences' own rows stay zero)."""
     lib = _native.load()
     dev = qkv.device
     rows, T = qkv.shape[0], plan.T
@@ -158,19 +160,19 @@ def attention_varlen_backward(qkv, ctx, dctx, lse, bits, plan, heads, scale, dro
     if rows > T:
         dqkv[T:].zero_()
     n3 = 3 * heads * 64
-    sp = plan.split() if long else None
-    M = plan.B + (sp["n_tiles"] if long else 0)
+    sp = plan.split()
+    M = plan.B + sp["n_tiles"]
     dsum = torch.zeros((M, n3), dtype=torch.float32, device=dev)
     p, seed, site = drop if drop is not None else (0.0, 0, 0)
     W = (plan.max_len + 31) // 32
     s = _native.stream_ptr(dev)
-    if long and sp["n_tiles"]:
+    if sp["n_tiles"]:
         _native.check(lib.drt_attention_varlen_long_backward_bf16(
             qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), plan.cu_seqlens.data_ptr(),
             sp["tiles"].data_ptr(), sp["n_tiles"], plan.max_len, plan.L, T, W, _ptr(bits), dqkv.data_ptr(),
             dsum[plan.B:].data_ptr(), heads, 64, float(scale), float(p), seed, site, s),
             "drt_attention_varlen_long_backward_bf16")
-    for ids, n, ml in plan.launches(per_class, "short" if long else None):
+    for ids, n, ml in plan.launches(per_class, "short"):
         _native.check(lib.drt_attention_varlen_backward_bf16(
             qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), plan.cu_seqlens.data_ptr(), ids, n, ml,
             plan.L, T, W, _ptr(bits), dqkv.data_ptr(), dsum.data_ptr(), heads, 64, float(scale), float(p), seed, site,

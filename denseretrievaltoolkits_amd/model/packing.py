@@ -39,17 +39,31 @@ hip_packed_train_min_saving = 0.15
 # of 0.06: 0.18.  DESIGN.md §5 "Padding-free training above 160 tokens".
 hip_packed_train_long_min_saving = 0.18
 
-# Attention length classes: ceil(len / 32) = 1 .. 5 run the kernels that hold the sequence's key
-# blocks in registers, class 0 (len > 160) the streamed form.
-_CLASS_MAX_BLOCKS = 5
-
-# The packed training tower (PackingPlan.split): sequences of at most _SHORT_MAX tokens run the
-# whole-sequence attention pair, longer ones the streamed pair over 128-row tiles.  The long forward's
-# launch classes follow its LDS image (260 B per padded key): up to 192 keys three work-groups share a
-# CU's 160 KiB, up to 288 two, beyond that one.
+# The whole-sequence attention kernels hold a sequence's key blocks in registers: ceil(len / 32) = 1 .. 5,
+# kAbMaxSeq of csrc/drt_common.h.  Longer sequences run the streamed forms -- in inference one class of
+# their own (class 0 of ``classes()``); in the packed training tower (``split()``) the streamed pair over
+# 128-row tiles, its forward's launch classes by LDS image (260 B per padded key): up to 192 keys three
+# work-groups share a CU's 160 KiB, up to 288 two, beyond that one.
 _SHORT_MAX = 160
+_CLASS_MAX_BLOCKS = _SHORT_MAX // 32
 _TILE_ROWS = 128
 _LONG_CLASS_MAX = (192, 288, 512)
+
+
+def _short_class(n: int) -> int:
+    return min((n + 31) // 32, _CLASS_MAX_BLOCKS + 1)
+
+
+class _OnFirstUse(dict):
+    """{key: build(key)}, each value built when it is first asked for."""
+
+    def __init__(self, build):
+        super().__init__()
+        self._build = build
+
+    def __missing__(self, key):
+        self[key] = self._build(key)
+        return self[key]
 
 
 @dataclass
@@ -83,26 +97,37 @@ class PackingPlan:
                                   self.L))]
         return self._halves
 
+    def _group(self, ids, class_of):
+        """{False: one launch over the sequences ``ids``, True: one per class ``class_of(len)``, longest
+        first}, each launch (seq_ids, n_seqs, max_len) with seq_ids a slice of one device tensor, or None
+        ("every sequence") where a single launch covers the whole batch.  A list is grouped, and its ids are
+        copied to the device, when it is first asked for: the grouping is O(B) on the host and the copy
+        waits for the stream, once per training step."""
+        if not ids:
+            return {False: [], True: []}
+
+        def build(per_class):
+            if not per_class and len(ids) == self.B:
+                return [(None, self.B, self.max_len)]
+            groups = {}
+            for b in ids:
+                groups.setdefault(class_of(self.lens[b]), []).append(b)
+            parts = [groups[c] for c in sorted(groups, reverse=True)]
+            launches = parts if per_class else [[b for part in parts for b in part]]
+            if len(launches) == 1 and len(ids) == self.B:
+                return [(None, self.B, self.max_len)]
+            flat = torch.tensor([b for part in parts for b in part], dtype=torch.int32).to(self.cu_seqlens.device)
+            ends = [sum(len(part) for part in launches[:i + 1]) for i in range(len(launches))]
+            return [(flat[e - len(part):e], len(part), max(self.lens[b] for b in part)) for part, e in zip(launches, ends)]
+
+        return _OnFirstUse(build)
+
     def classes(self):
         """One (seq_ids, n_seqs, max_len) per attention launch: the sequences grouped by
-        ceil(len / 32) up to 5 blocks, longer ones together.  A batch of one class needs no list."""
+        ceil(len / 32) up to 5 blocks, longer ones together (class 0, first).  A batch of one class needs
+        no list."""
         if self._classes is None:
-            groups = {}
-            for b, n in enumerate(self.lens):
-                nb = (n + 31) // 32
-                groups.setdefault(nb if nb <= _CLASS_MAX_BLOCKS else 0, []).append(b)
-            if len(groups) == 1:
-                self._classes = [(None, self.B, self.max_len)]
-            else:
-                order = sorted(groups, key=lambda c: (c == 0, c), reverse=True)   # longest first
-                flat = torch.tensor([b for c in order for b in groups[c]], dtype=torch.int32)
-                flat = flat.to(self.cu_seqlens.device)
-                out, at = [], 0
-                for c in order:
-                    ids = groups[c]
-                    out.append((flat[at:at + len(ids)], len(ids), max(self.lens[b] for b in ids)))
-                    at += len(ids)
-                self._classes = out
+            self._classes = self._group(list(range(self.B)), _short_class)[True]
         return self._classes
 
     def split(self):
@@ -112,41 +137,23 @@ class PackingPlan:
         by length class as ``classes()``, the long ones by the LDS image of the forward: up to
         ``_LONG_CLASS_MAX`` tokens each); ``tiles``: device int32 [n_tiles, 2] = (sequence, 128-row
         group) of every group of a long sequence that holds a token, a sequence's groups adjacent;
-        ``n_tiles``."""
+        ``n_tiles``.  With no sequence over 160 tokens the long part and the tile table are empty and the
+        short part is ``launches(per_class)``."""
         if self._split is None:
-            dev = self.cu_seqlens.device
-            short = [b for b, n in enumerate(self.lens) if n <= _SHORT_MAX]
-            long_ = [b for b, n in enumerate(self.lens) if n > _SHORT_MAX]
+            long_ = [b for b, n in enumerate(self.lens) if n > _SHORT_MAX] if self.max_len > _SHORT_MAX else []
+            short = [b for b, n in enumerate(self.lens) if n <= _SHORT_MAX] if long_ else list(range(self.B))
             tiles = [(b, g) for b in long_ for g in range((self.lens[b] + _TILE_ROWS - 1) // _TILE_ROWS)]
-
-            def part(ids, class_of):
-                if not ids:
-                    return {False: [], True: []}
-                groups = {}
-                for b in ids:
-                    groups.setdefault(class_of(self.lens[b]), []).append(b)
-                order = sorted(groups, reverse=True)                          # longest first
-                flat = torch.tensor([b for c in order for b in groups[c]], dtype=torch.int32).to(dev)
-                whole = None if len(ids) == self.B else flat                 # every sequence: no list
-                out, at = [], 0
-                for c in order:
-                    n = len(groups[c])
-                    out.append((flat[at:at + n] if len(order) > 1 or whole is not None else None, n,
-                                max(self.lens[b] for b in groups[c])))
-                    at += n
-                return {False: [(whole, len(ids), max(self.lens[b] for b in ids))], True: out}
-
             self._split = {
-                "short": part(short, lambda n: (n + 31) // 32),
-                "long": part(long_, lambda n: next(i for i, m in enumerate(_LONG_CLASS_MAX) if n <= m)),
-                "tiles": torch.tensor(tiles, dtype=torch.int32).reshape(-1, 2).to(dev), "n_tiles": len(tiles)}
+                "short": self._group(short, _short_class),
+                "long": self._group(long_, lambda n: next(i for i, m in enumerate(_LONG_CLASS_MAX) if n <= m)),
+                "tiles": torch.tensor(tiles, dtype=torch.int32, device=self.cu_seqlens.device).reshape(-1, 2),
+                "n_tiles": len(tiles)}
         return self._split
 
     def launches(self, per_class: bool, part: Optional[str] = None):
         """The (seq_ids pointer or None, n_seqs, max_len) of each varlen attention launch over the batch,
-        forward or backward: one per length class (``classes()``), or one for the whole batch.  Callers
-        build it once per pass, outside their layer loop.  ``part`` = "short" / "long": the launches of
-        that part of ``split()`` instead."""
+        forward or backward: one per length class (``classes()``), or one for the whole batch.  ``part`` =
+        "short" / "long": the launches of that part of ``split()`` instead."""
         launches = self.split()[part][bool(per_class)] if part else \
             self.classes() if per_class else [(None, self.B, self.max_len)]
         return [(s.data_ptr() if s is not None else None, n, ml) for s, n, ml in launches]

@@ -36,11 +36,12 @@ never touch it), ``pack_rows`` zeroes the tail of the incoming gradient, and the
 dropout and dgrad of a zero gradient row are zero.  Hidden-site dropout uses the existing kernels and
 GEMM epilogues unchanged, so element (t, j) of a packed matrix draws index ``t * H + j``: the same
 distribution as the padded run, different draws; the attention keeps of every real (query, key) ARE
-the padded run's (the hash takes the padded row).  A plan with ``max_len > 160`` keeps the padded
-tower, logged once, unless ``hip_packed_train_long`` is set as well (``train_hidden(..., packed_long=True)``):
-then the sequences over 160 tokens, up to 512, run the varlen forms of the streamed attention pair
-(``drt_attention_varlen_long_train_forward_bf16`` / ``..._long_backward_bf16`` over the plan's tile table) and
-the shorter ones of the same batch the whole-sequence pair.
+the padded run's (the hash takes the padded row).  The attention pair routes every plan by
+``PackingPlan.split()``: the sequences over 160 tokens, up to 512, run the varlen forms of the streamed
+pair (``drt_attention_varlen_long_train_forward_bf16`` / ``..._long_backward_bf16`` over the plan's tile
+table), the shorter ones of the same batch the whole-sequence pair.  A plan with ``max_len > 160`` is
+accepted only with ``hip_packed_train_long`` (``train_hidden(..., packed_long=True)``); otherwise it keeps
+the padded tower, logged once.
 """
 from __future__ import annotations
 
@@ -53,13 +54,13 @@ from .encoder import BertShape, _check_supported, bert_weights
 from .encoder_bwd import (LIN_GELU, _ptr, attention_backward, attention_forward, attention_varlen_backward,
                           attention_varlen_forward, dropout, grads_out, layernorm_backward, linear, linear_backward,
                           pack_rows, transpose_bf16, unpack_rows)
+from .packing import _SHORT_MAX
 
 MAX_TRAIN_SEQ = 512
-# kAbMaxSeq of csrc/drt_common.h: the whole-sequence attention backward (the streamed one has no varlen
-# form).  tests/test_packed_train_host_cpu.py pins it to what the two varlen training entries accept.
-MAX_PACKED_TRAIN_LEN = 160
-# kAblMaxSeq: the streamed pair's varlen forms, behind hip_packed_train_long
-# (tests/test_packed_train_long_host_cpu.py pins it to what the two long entries accept).
+# The longest sequence a plan may hold without / with hip_packed_train_long: kAbMaxSeq (the whole-sequence
+# attention pair, where PackingPlan.split() cuts) and kAblMaxSeq (the streamed pair's varlen forms).
+# tests/test_packed_train_entries_host_cpu.py pins both to what the four varlen training entries accept.
+MAX_PACKED_TRAIN_LEN = _SHORT_MAX
 MAX_PACKED_TRAIN_LONG_LEN = 512
 
 # Attention launches of the packed tower: False = one launch per batch (forward and backward), True =
@@ -121,8 +122,6 @@ class _Step:
         self.types = types   # token_type_ids [B, L] int64 or None (all type 0)
         self.B, self.L = ids.shape
         self.plan = plan     # PackingPlan: the tower runs on ``rows`` packed rows, of which plan.T are tokens
-        # a sequence over MAX_PACKED_TRAIN_LEN tokens: the attention pair routes by plan.split()
-        self.long = plan is not None and plan.max_len > MAX_PACKED_TRAIN_LEN
         self.rows = (plan.T + 31) // 32 * 32 if plan is not None else self.B * self.L
         self.H, self.heads, self.eps = cfg.hidden_size, cfg.num_attention_heads, float(cfg.layer_norm_eps)
         self.scale = 1.0 / (self.H // self.heads) ** 0.5
@@ -193,7 +192,7 @@ def layer_forward(st: _Step, i: int, h):
     qkv = linear(h, ly["wqkv"], torch.empty((T, 3 * H), dtype=torch.bfloat16, device=dev), bias=ly["bqkv"])
     if st.plan is not None:
         ctx, lse, bits = attention_varlen_forward(qkv, st.plan, heads, st.scale, drop=(pa, seed, s_att),
-                                                  per_class=packed_train_classes, long=st.long)
+                                                  per_class=packed_train_classes)
     else:
         ctx, lse, bits = attention_forward(qkv, st.mask, B, L, heads, st.scale, drop=(pa, seed, s_att))
     # x1 = dropout(ctx Wo^T + bo) + h, dropout in the GEMM epilogue
@@ -238,7 +237,7 @@ def layer_backward(st: _Step, i: int, saved, d) -> Tuple[torch.Tensor, Dict[str,
     # gradients without a pass over dQKV
     if st.plan is not None:
         dqkv, dbqkv = attention_varlen_backward(qkv, ctx, dctx, lse, bits, st.plan, heads, st.scale,
-                                                drop=(pa, seed, s_att), per_class=packed_train_classes, long=st.long)
+                                                drop=(pa, seed, s_att), per_class=packed_train_classes)
     else:
         dqkv, dbqkv = attention_backward(qkv, ctx, dctx, lse, st.mask, bits, st.B, st.L, heads, st.scale,
                                          drop=(pa, seed, s_att), want_dbias=True)
@@ -333,8 +332,9 @@ def train_hidden(model, input_ids: torch.Tensor, attention_mask: Optional[torch.
     if why is not None:
         raise NotImplementedError(f"HIP training tower: {why}")
     if plan is not None:
-        if plan.max_len > (MAX_PACKED_TRAIN_LONG_LEN if packed_long else MAX_PACKED_TRAIN_LEN):
-            _log_fallback(f"hip_packed_train: padded tower, longest sequence {plan.max_len} > {MAX_PACKED_TRAIN_LEN}")
+        limit = MAX_PACKED_TRAIN_LONG_LEN if packed_long else MAX_PACKED_TRAIN_LEN
+        if plan.max_len > limit:
+            _log_fallback(f"hip_packed_train: padded tower, longest sequence {plan.max_len} > {limit}")
             plan = None
         elif (plan.B, plan.L) != tuple(input_ids.shape):
             _log_fallback("hip_packed_train: padded tower, the plan is of another batch shape")

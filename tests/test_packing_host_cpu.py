@@ -58,6 +58,42 @@ def test_plan_launches():
     assert one.launches(per_class=True) == one.launches(per_class=False) == [(None, 3, 30)]
 
 
+def _host(launches):
+    """[(id list or None, n, max_len)] of a plan's launch tuples, read back from the tensors."""
+    return [(None if ids is None else ids.tolist(), n, ml) for ids, n, ml in launches]
+
+
+@pytest.mark.parametrize("lens", [[5, 160, 33, 64, 32, 1], [3, 30, 17], [160]], ids=["classes", "one_class", "single"])
+def test_split_of_a_short_plan_is_its_launches(lens):
+    """With no sequence over 160 tokens the short part of split() IS launches(per_class), the long part
+    and the tile table are empty: why the training tower routes every plan through split()."""
+    from denseretrievaltoolkits_amd.model.packing import plan_packing
+    plan = plan_packing(_prefix_mask(lens, 192), 192)
+    sp = plan.split()
+    assert sp["n_tiles"] == 0 and sp["tiles"].shape == (0, 2)
+    for pc in (False, True):
+        whole = plan.classes() if pc else [(None, plan.B, plan.max_len)]
+        assert _host(sp["short"][pc]) == _host(whole)
+        assert [(p is None, n, ml) for p, n, ml in plan.launches(pc, "short")] == \
+            [(p is None, n, ml) for p, n, ml in plan.launches(pc)]
+        assert plan.launches(pc, "long") == [] and sp["long"][pc] == []
+    if len({(n + 31) // 32 for n in lens}) == 1:
+        assert _host(sp["short"][True]) == [(None, len(lens), max(lens))]
+    else:
+        assert _host(sp["short"][True]) == [([1], 1, 160), ([2, 3], 2, 64), ([0, 4, 5], 3, 32)]
+    assert _host(sp["short"][False]) == [(None, len(lens), max(lens))]
+
+
+def test_classes_and_long_part_are_ordered_longest_first():
+    from denseretrievaltoolkits_amd.model.packing import plan_packing
+    plan = plan_packing(_prefix_mask([5, 200, 33, 64, 161, 32, 1], 256), 256)
+    # the class of more than 5 blocks first, then the blocks in descending order; ids in batch order
+    assert _host(plan.classes()) == [([1, 4], 2, 200), ([2, 3], 2, 64), ([0, 5, 6], 3, 32)]
+    plan = plan_packing(_prefix_mask([300, 40, 256, 161, 160, 257, 512, 128], 512), 512)
+    assert [ml for _, _, ml in plan.split()["long"][True]] == [512, 257, 161]
+    assert _host(plan.split()["short"][True]) == [([4], 1, 160), ([7], 1, 128), ([1], 1, 40)]
+
+
 @pytest.mark.parametrize("kind", ["holes", "left", "allzero_row", "none", "full"])
 def test_no_plan(kind):
     import torch

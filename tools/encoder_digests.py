@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """sha256 digests of the encoder paths' outputs for one source tree, to show that a host-side change
 leaves every bit alone: padded / packed / two-stream BERT forward, pooling, unpack, the training tower's
-output and parameter gradients (padded and packed), and the T5 encoder, on tiny seeded models.
+output and parameter gradients (padded, packed, and packed above 160 tokens), and the T5 encoder, on tiny seeded models.
 
 Run it once per tree, each in a fresh process, and compare the two files, e.g. against the parent commit:
     git archive HEAD~1 | tar -x -C /tmp/parent && (cd /tmp/parent && python -m denseretrievaltoolkits_amd.build_native)
@@ -83,6 +83,22 @@ for packed in (False, True):
     dig(f"train_hidden {tag} out", out)
     for n, p in model.named_parameters():
         dig(f"train_hidden {tag} grad {n}", p.grad)
+
+# packed training above 160 tokens (packed_long): both sides of the 160 / 161 boundary in one batch, and a
+# 512-token sequence; dropout on and off
+for B, L, lens in ((4, 192, [161, 5, 160, 33]), (3, 512, [512, 40, 200])):
+    ids, mask = batch(B, L, lens, 50 + B)
+    fixed = torch.randn((B, L, 256), generator=torch.Generator().manual_seed(51)).to(dev)
+    for p in (0.1, 0.0):
+        cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = p
+        model.zero_grad(set_to_none=True)
+        out = train_hidden(model, ids, mask, seed=4321, plan=plan_packing(mask, L, device=dev, min_saving=0.0),
+                           packed_long=True)
+        (out * fixed).sum().backward()
+        dig(f"train_hidden packed_long [{B},{L}] p={p} out", out)
+        for n, par in model.named_parameters():
+            dig(f"train_hidden packed_long [{B},{L}] p={p} grad {n}", par.grad)
+cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = 0.1
 model.eval()
 
 torch.manual_seed(2)

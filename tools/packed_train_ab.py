@@ -80,7 +80,6 @@ def main():
     lib = _native.load()
     rec = {"tool": "tools/packed_train_ab.py", "steps": args.steps, "rounds": args.rounds,
            "pkg_root": os.path.relpath(args.pkg_root), "device": torch.cuda.get_device_name(0), "shapes": {}}
-    long = {"long": True} if args.long else {}
     for name, B, L, lo, hi in (LONG_SHAPES if args.long else SHAPES):
         g = torch.Generator().manual_seed(B * 1000 + L)
         lens = torch.randint(lo, hi + 1, (B,), generator=g)
@@ -139,7 +138,7 @@ def main():
             qkv_t, dctx_t = qkv_p[sel].contiguous(), dctx_p[sel].contiguous()
             drop = (0.1, 1234, 1)
             ctx_p, lse_p, bits_p = encoder_bwd.attention_forward(qkv_p, mask, B, L, heads, 0.125, drop=drop)
-            ctx_t, lse_t, bits_t = encoder_bwd.attention_varlen_forward(qkv_t, plan, heads, 0.125, drop=drop, **long)
+            ctx_t, lse_t, bits_t = encoder_bwd.attention_varlen_forward(qkv_t, plan, heads, 0.125, drop=drop)
 
             def bwd_padded():
                 encoder_bwd.attention_backward(qkv_p, ctx_p, dctx_p, lse_p, mask, bits_p, B, L, heads, 0.125, drop=drop,
@@ -147,11 +146,11 @@ def main():
 
             def bwd_varlen(classes):
                 return lambda: encoder_bwd.attention_varlen_backward(qkv_t, ctx_t, dctx_t, lse_t, bits_t, plan, heads,
-                                                                      0.125, drop=drop, per_class=classes, **long)
+                                                                      0.125, drop=drop, per_class=classes)
 
             def fwd_varlen(classes):
                 return lambda: encoder_bwd.attention_varlen_forward(qkv_t, plan, heads, 0.125, drop=drop,
-                                                                     per_class=classes, **long)
+                                                                     per_class=classes)
 
             attn = {"bwd_padded": bwd_padded, "bwd_varlen_one_launch": bwd_varlen(False),
                     "bwd_varlen_classes": bwd_varlen(True),
