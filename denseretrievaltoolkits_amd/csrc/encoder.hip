@@ -124,14 +124,8 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* X, int6
   const int lane = threadIdx.x & 63;
   const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= M) return;
-  const float* xr = X + t * H;
   float x[EPL];
-#pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const f32x4 a = *(const f32x4*)(xr + e4 * 256 + lane * 4);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) x[e4 * 4 + u] = a[u];
-  }
+  row_load<EPL>(X + t * H, lane, x);
   ln_row<EPL>(x, gamma, beta, eps, lane, H, out + t * H);
 }
 
@@ -148,35 +142,28 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const __bf16* X, in
   const int64_t t0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nw = (int64_t)gridDim.x * 4;
   if (t0 >= M) return;
+  using RC = RowChunks<EPL>;
   float g[EPL], b[EPL];
+  row_load<EPL>(gamma, lane, g);
+  row_load<EPL>(beta, lane, b);
+  bf16v<RC::W> cur[RC::N];
 #pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const f32x4 gv = *(const f32x4*)(gamma + e4 * 256 + lane * 4);
-    const f32x4 bv = *(const f32x4*)(beta + e4 * 256 + lane * 4);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      g[e4 * 4 + u] = gv[u];
-      b[e4 * 4 + u] = bv[u];
-    }
-  }
-  bf16x4 cur[EPL / 4];
-#pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) cur[e4] = *(const bf16x4*)(X + t0 * H + e4 * 256 + lane * 4);
+  for (int j = 0; j < RC::N; ++j) cur[j] = *(const bf16v<RC::W>*)(X + t0 * H + j * RC::STRIDE + lane * RC::W);
   for (int64_t t = t0; t < M; t += nw) {
     const int64_t tn = t + nw;
-    bf16x4 nxt[EPL / 4];
+    bf16v<RC::W> nxt[RC::N];
     if (tn < M) {
 #pragma unroll
-      for (int e4 = 0; e4 < EPL / 4; ++e4) nxt[e4] = *(const bf16x4*)(X + tn * H + e4 * 256 + lane * 4);
+      for (int j = 0; j < RC::N; ++j) nxt[j] = *(const bf16v<RC::W>*)(X + tn * H + j * RC::STRIDE + lane * RC::W);
     }
     float x[EPL];
 #pragma unroll
-    for (int e4 = 0; e4 < EPL / 4; ++e4)
+    for (int j = 0; j < RC::N; ++j)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) x[e4 * 4 + u] = (float)cur[e4][u];
+      for (int u = 0; u < RC::W; ++u) x[j * RC::W + u] = (float)cur[j][u];
     ln_row_gb<EPL>(x, g, b, eps, lane, H, out + t * H);
 #pragma unroll
-    for (int e4 = 0; e4 < EPL / 4; ++e4) cur[e4] = nxt[e4];
+    for (int j = 0; j < RC::N; ++j) cur[j] = nxt[j];
   }
 }
 
@@ -269,16 +256,17 @@ int drt_embedding_bwd(const int64_t* ids, const int64_t* type_ids, int32_t ntype
   return hip_status(hipGetLastError());
 }
 
-int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
-                     const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
-                     int32_t H, void* out, void* pre, void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && H > 0 && H % 256 == 0 && H <= 1024);
+// drt_embed_ln (h384: H = 384 too, the inference entry) and drt_embed_ln_pre
+static int embed_ln_entry(bool h384, const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L,
+                          const float* word_emb, const float* pos_emb, const float* type_emb, const float* gamma,
+                          const float* beta, float eps, int32_t H, void* out, void* pre, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && H > 0 && (H % 256 == 0 || (h384 && H == 384)) && H <= 1024);
   const int64_t T = B * L;
   if (T == 0) return DRT_OK;
   DRT_REQUIRE(ids && word_emb && pos_emb && type_emb && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((T + 3) / 4));
-  if (const int rc = dispatch_epl(H, [&](auto E) {
+  if (const int rc = dispatch_epl_or_384(H, [&](auto E) {
         hipLaunchKernelGGL(embed_ln_kernel<decltype(E)::value>, grid, dim3(256), 0, s, ids, type_ids, T, L, word_emb,
                            pos_emb, type_emb, gamma, beta, eps, (int)H, (__bf16*)out, (__bf16*)pre);
       }))
@@ -286,20 +274,27 @@ int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int
   return hip_status(hipGetLastError());
 }
 
+int drt_embed_ln_pre(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
+                     const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
+                     int32_t H, void* out, void* pre, void* stream) {
+  return embed_ln_entry(false, ids, type_ids, B, L, word_emb, pos_emb, type_emb, gamma, beta, eps, H, out, pre, stream);
+}
+
 int drt_embed_ln(const int64_t* ids, const int64_t* type_ids, int64_t B, int64_t L, const float* word_emb,
                  const float* pos_emb, const float* type_emb, const float* gamma, const float* beta, float eps,
                  int32_t H, void* out, void* stream) {
-  return drt_embed_ln_pre(ids, type_ids, B, L, word_emb, pos_emb, type_emb, gamma, beta, eps, H, out, nullptr, stream);
+  return embed_ln_entry(true, ids, type_ids, B, L, word_emb, pos_emb, type_emb, gamma, beta, eps, H, out, nullptr,
+                        stream);
 }
 
 int drt_layernorm_f32_bf16(const float* X, int64_t M, int32_t H, const float* gamma, const float* beta, float eps,
                            void* out, void* stream) {
-  DRT_REQUIRE(M >= 0 && H > 0 && H % 256 == 0 && H <= 1024);
+  DRT_REQUIRE(M >= 0 && H > 0 && (H % 256 == 0 || H == 384) && H <= 1024);
   if (M == 0) return DRT_OK;
   DRT_REQUIRE(X && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((M + 3) / 4));
-  if (const int rc = dispatch_epl(H, [&](auto E) {
+  if (const int rc = dispatch_epl_or_384(H, [&](auto E) {
         hipLaunchKernelGGL(layernorm_f32_kernel<decltype(E)::value>, grid, dim3(256), 0, s, X, M, H, gamma, beta, eps,
                            (__bf16*)out);
       }))
@@ -309,12 +304,12 @@ int drt_layernorm_f32_bf16(const float* X, int64_t M, int32_t H, const float* ga
 
 int drt_layernorm_bf16(const void* X, int64_t M, int32_t H, const float* gamma, const float* beta, float eps,
                        void* out, void* stream) {
-  DRT_REQUIRE(M >= 0 && H > 0 && H % 256 == 0 && H <= 1024);
+  DRT_REQUIRE(M >= 0 && H > 0 && (H % 256 == 0 || H == 384) && H <= 1024);
   if (M == 0) return DRT_OK;
   DRT_REQUIRE(X && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(ln_rows_grid(M));
-  if (const int rc = dispatch_epl(H, [&](auto E) {
+  if (const int rc = dispatch_epl_or_384(H, [&](auto E) {
         hipLaunchKernelGGL(layernorm_bf16_kernel<decltype(E)::value>, grid, dim3(256), 0, s, (const __bf16*)X, M, H,
                            gamma, beta, eps, (__bf16*)out);
       }))

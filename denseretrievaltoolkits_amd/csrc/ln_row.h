@@ -1,11 +1,38 @@
 // Row LayerNorm helpers shared by the encoder kernels and the GEMM's fused split-K + LayerNorm
-// finish (one wave per row, H = 64 * EPL, EPL a multiple of 4 and <= 16).
+// finish (one wave per row, H = 64 * EPL, EPL <= 16).
 #pragma once
 #include <type_traits>
 
 #include "drt_common.h"
 
 namespace drt {
+
+// The row layout, stated once: a lane's EPL elements are EPL / W chunks of W consecutive columns,
+// element e = column (e / W) * 64 W + lane * W + e % W.  W = 4 when EPL is a multiple of 4 (256-column
+// chunks: 16-B fp32 loads, 8-B bf16 stores -- H = 256 .. 1024), else 2 (EPL = 6, H = 384: three
+// 128-column chunks of 8-B fp32 loads and 4-B bf16 stores).  The sums run over e in order whatever W is.
+template <int EPL>
+struct RowChunks {
+  static_assert(EPL % 2 == 0 && EPL <= 16, "row kernels: an even number of elements per lane, H <= 1024");
+  static constexpr int W = EPL % 4 == 0 ? 4 : 2, N = EPL / W, STRIDE = 64 * W;
+};
+template <int W>
+using f32v = float __attribute__((ext_vector_type(W)));
+template <int W>
+using bf16v = __bf16 __attribute__((ext_vector_type(W)));
+
+// x[e] = (float)row[column of e]: the lane's part of an fp32 or bf16 row
+template <int EPL, typename T>
+__device__ __forceinline__ void row_load(const T* row, int lane, float (&x)[EPL]) {
+  using RC = RowChunks<EPL>;
+  typedef T vec __attribute__((ext_vector_type(RC::W)));
+#pragma unroll
+  for (int j = 0; j < RC::N; ++j) {
+    const vec a = *(const vec*)(row + j * RC::STRIDE + lane * RC::W);
+#pragma unroll
+    for (int u = 0; u < RC::W; ++u) x[j * RC::W + u] = (float)a[u];
+  }
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -28,14 +55,14 @@ __device__ __forceinline__ void ln_row(float (&x)[EPL], const float* gamma, cons
   }
   const float var = wave_sum(v) / (float)H;
   const float rstd = rsqrtf(var + eps);
-  // element e of lane: column c = (e / 4) * 256 + lane * 4 + (e % 4)   (4-wide chunks)
+  using RC = RowChunks<EPL>;
 #pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const int c = e4 * 256 + lane * 4;
-    bf16x4 o;
+  for (int j = 0; j < RC::N; ++j) {
+    const int c = j * RC::STRIDE + lane * RC::W;
+    bf16v<RC::W> o;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) o[u] = (__bf16)((x[e4 * 4 + u] - mean) * rstd * gamma[c + u] + beta[c + u]);
-    *(bf16x4*)(out_row + c) = o;
+    for (int u = 0; u < RC::W; ++u) o[u] = (__bf16)((x[j * RC::W + u] - mean) * rstd * gamma[c + u] + beta[c + u]);
+    *(bf16v<RC::W>*)(out_row + c) = o;
   }
 }
 
@@ -50,26 +77,27 @@ __device__ __forceinline__ void embed_ln_row(int64_t id, int64_t tt, int64_t pos
   const float* w = wemb + id * H;
   const float* p = pemb + pos * H;
   const float* y = temb + tt * H;
+  using RC = RowChunks<EPL>;
   float x[EPL];
 #pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const int c = e4 * 256 + lane * 4;
-    const f32x4 a = *(const f32x4*)(w + c);
-    const f32x4 b = *(const f32x4*)(p + c);
-    const f32x4 d = *(const f32x4*)(y + c);
+  for (int j = 0; j < RC::N; ++j) {
+    const int c = j * RC::STRIDE + lane * RC::W;
+    const f32v<RC::W> a = *(const f32v<RC::W>*)(w + c);
+    const f32v<RC::W> b = *(const f32v<RC::W>*)(p + c);
+    const f32v<RC::W> d = *(const f32v<RC::W>*)(y + c);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) x[e4 * 4 + u] = (a[u] + d[u]) + b[u];  // (word + type) + position, as HF
+    for (int u = 0; u < RC::W; ++u) x[j * RC::W + u] = (a[u] + d[u]) + b[u];  // (word + type) + position, as HF
     if (pre) {   // training forward: the pre-LN sum, input of the LayerNorm backward
-      bf16x4 o;
+      bf16v<RC::W> o;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (__bf16)x[e4 * 4 + u];
-      *(bf16x4*)(pre + t * H + c) = o;
+      for (int u = 0; u < RC::W; ++u) o[u] = (__bf16)x[j * RC::W + u];
+      *(bf16v<RC::W>*)(pre + t * H + c) = o;
     }
   }
   ln_row<EPL>(x, gamma, beta, eps, lane, H, out + t * H);
 }
 
-// ln_row with gamma / beta already in registers (g[e], b[e] of column (e / 4) * 256 + lane * 4 + e % 4):
+// ln_row with gamma / beta already in registers (g[e], b[e] of element e's column, RowChunks):
 // the same arithmetic in the same order, for kernels that normalise many rows per wave.
 template <int EPL>
 __device__ __forceinline__ void ln_row_gb(float (&x)[EPL], const float (&g)[EPL], const float (&b)[EPL], float eps,
@@ -86,13 +114,14 @@ __device__ __forceinline__ void ln_row_gb(float (&x)[EPL], const float (&g)[EPL]
   }
   const float var = wave_sum(v) / (float)H;
   const float rstd = rsqrtf(var + eps);
+  using RC = RowChunks<EPL>;
 #pragma unroll
-  for (int e4 = 0; e4 < EPL / 4; ++e4) {
-    const int c = e4 * 256 + lane * 4;
-    bf16x4 o;
+  for (int j = 0; j < RC::N; ++j) {
+    const int c = j * RC::STRIDE + lane * RC::W;
+    bf16v<RC::W> o;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) o[u] = (__bf16)((x[e4 * 4 + u] - mean) * rstd * g[e4 * 4 + u] + b[e4 * 4 + u]);
-    *(bf16x4*)(out_row + c) = o;
+    for (int u = 0; u < RC::W; ++u) o[u] = (__bf16)((x[j * RC::W + u] - mean) * rstd * g[j * RC::W + u] + b[j * RC::W + u]);
+    *(bf16v<RC::W>*)(out_row + c) = o;
   }
 }
 
@@ -123,6 +152,17 @@ inline int dispatch_epl(int64_t H, F&& f) {
     case 16: f(std::integral_constant<int, 16>{}); return DRT_OK;
     default: return DRT_EINVAL;
   }
+}
+
+// The same plus H = 384 (EPL = 6, MiniLM-class towers): the inference row entries only -- drt_embed_ln,
+// drt_embed_ln_packed and the two LayerNorms.
+template <typename F>
+inline int dispatch_epl_or_384(int64_t H, F&& f) {
+  if (H == 384) {
+    f(std::integral_constant<int, 6>{});
+    return DRT_OK;
+  }
+  return dispatch_epl(H, f);
 }
 
 }  // namespace drt

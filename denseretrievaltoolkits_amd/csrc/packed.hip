@@ -113,17 +113,18 @@ using namespace drt;
 
 extern "C" {
 
-int drt_embed_ln_pre_packed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, int64_t B,
-                            int64_t L, int64_t T, const float* word_emb, const float* pos_emb, const float* type_emb,
-                            const float* gamma, const float* beta, float eps, int32_t H, void* out, void* pre,
-                            void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && T >= 0 && H > 0 && H % 256 == 0 && H <= 1024);
+// drt_embed_ln_packed (h384: H = 384 too, the inference entry) and drt_embed_ln_pre_packed
+static int embed_ln_packed_entry(bool h384, const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens,
+                                 int64_t B, int64_t L, int64_t T, const float* word_emb, const float* pos_emb,
+                                 const float* type_emb, const float* gamma, const float* beta, float eps, int32_t H,
+                                 void* out, void* pre, void* stream) {
+  DRT_REQUIRE(B >= 0 && L > 0 && T >= 0 && H > 0 && (H % 256 == 0 || (h384 && H == 384)) && H <= 1024);
   DRT_REQUIRE(B < (1ll << 31) && T < (1ll << 31) && T <= B * L);
   if (B == 0 || T == 0) return DRT_OK;
   DRT_REQUIRE(ids && cu_seqlens && word_emb && pos_emb && type_emb && gamma && beta && out);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((T + 3) / 4));
-  if (const int rc = dispatch_epl(H, [&](auto E) {
+  if (const int rc = dispatch_epl_or_384(H, [&](auto E) {
         hipLaunchKernelGGL(embed_ln_packed_kernel<decltype(E)::value>, grid, dim3(256), 0, s, ids, type_ids, cu_seqlens,
                            (int)B, L, (int)T, word_emb, pos_emb, type_emb, gamma, beta, eps, (int)H, (__bf16*)out,
                            (__bf16*)pre);
@@ -132,11 +133,19 @@ int drt_embed_ln_pre_packed(const int64_t* ids, const int64_t* type_ids, const i
   return hip_status(hipGetLastError());
 }
 
+int drt_embed_ln_pre_packed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, int64_t B,
+                            int64_t L, int64_t T, const float* word_emb, const float* pos_emb, const float* type_emb,
+                            const float* gamma, const float* beta, float eps, int32_t H, void* out, void* pre,
+                            void* stream) {
+  return embed_ln_packed_entry(false, ids, type_ids, cu_seqlens, B, L, T, word_emb, pos_emb, type_emb, gamma, beta, eps,
+                               H, out, pre, stream);
+}
+
 int drt_embed_ln_packed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, int64_t B, int64_t L,
                         int64_t T, const float* word_emb, const float* pos_emb, const float* type_emb,
                         const float* gamma, const float* beta, float eps, int32_t H, void* out, void* stream) {
-  return drt_embed_ln_pre_packed(ids, type_ids, cu_seqlens, B, L, T, word_emb, pos_emb, type_emb, gamma, beta, eps, H,
-                                 out, nullptr, stream);
+  return embed_ln_packed_entry(true, ids, type_ids, cu_seqlens, B, L, T, word_emb, pos_emb, type_emb, gamma, beta, eps,
+                               H, out, nullptr, stream);
 }
 
 int drt_pool_packed_bf16(const void* hidden, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H, int32_t mode,

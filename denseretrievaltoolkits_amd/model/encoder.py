@@ -63,6 +63,21 @@ def _check_supported(shape: BertShape):
         raise ValueError("only erf GELU ('gelu') is implemented")
 
 
+def _check_inference_supported(shape: BertShape):
+    """The inference encoder's gate: the training tower's shapes (``_check_supported``, which stays that
+    tower's gate) plus MiniLM-class towers -- hidden 384 at head_dim 32 with an even head count, served
+    by the head_dim-32 attention (csrc/attention_hd32.hip) and the H = 384 row kernels."""
+    if shape.hidden == 384 and shape.heads > 0 and shape.hidden // shape.heads == 32 and shape.hidden % shape.heads == 0:
+        if shape.heads % 2:
+            raise ValueError("head_dim 32 needs an even head count (one work-group per head pair)")
+        if shape.intermediate % 64:
+            raise ValueError("intermediate size must be a multiple of 64")
+        if shape.act != "gelu":
+            raise ValueError("only erf GELU ('gelu') is implemented")
+        return
+    _check_supported(shape)
+
+
 def linear_ws(lib, x, w, b, resid, out, flags, ws, stream):
     """out = act(x w^T + b) (+ resid) through drt_linear_bf16_ws with the caller's split-K scratch ``ws``
     (fp32 tensor or None): the ``_lin`` of every inference encoder / decoder."""
@@ -132,7 +147,7 @@ class HipBertEncoder:
 
     def __init__(self, shape: BertShape, state: Dict[str, torch.Tensor], device: torch.device,
                  prefix: str = "", presum: str = "bf16"):
-        _check_supported(shape)
+        _check_inference_supported(shape)
         if presum not in ("bf16", "fp32"):
             raise ValueError(f"presum must be 'bf16' or 'fp32', got {presum!r}")
         self.presum = presum
@@ -298,18 +313,28 @@ class HipBertEncoder:
         ffn = torch.empty((T, sh.intermediate), dtype=torch.bfloat16, device=dev)
         nb = self._ws_bytes(T)
         self._ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev) if nb else None
-        scale = 1.0 / math.sqrt(H // sh.heads)
+        dh = H // sh.heads
+        scale = 1.0 / math.sqrt(dh)
         mp = mask.data_ptr() if mask is not None else None
         for ly in self.layers:
             self._lin(h, ly["wqkv"], ly["bqkv"], qkv)
-            if plan is None:
+            if plan is None and dh == 32:
+                _native.check(self.lib.drt_attention_hd32_forward_bf16(qkv.data_ptr(), mp, ctx.data_ptr(), B, L,
+                                                                       sh.heads, scale, self.stream),
+                              "drt_attention_hd32_forward_bf16")
+            elif plan is None:
                 _native.check(self.lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, None, ctx.data_ptr(), None, None,
-                                                                  B, L, sh.heads, H // sh.heads, scale, 0.0, 0, 0,
+                                                                  B, L, sh.heads, dh, scale, 0.0, 0, 0,
                                                                   self.stream), "drt_attention_forward_bf16")
+            elif dh == 32:
+                for sp, n, ml in launches:
+                    _native.check(self.lib.drt_attention_hd32_varlen_forward_bf16(
+                        qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(), sh.heads, scale, self.stream),
+                        "drt_attention_hd32_varlen_forward_bf16")
             else:
                 for sp, n, ml in launches:
                     _native.check(self.lib.drt_attention_varlen_forward_bf16(
-                        qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(), sh.heads, H // sh.heads, scale, self.stream),
+                        qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(), sh.heads, dh, scale, self.stream),
                         "drt_attention_varlen_forward_bf16")
             self._lin_ln(ctx, ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], x32, ln)
             self._lin(h, ly["wi"], ly["bi"], ffn, gelu=True)

@@ -344,7 +344,7 @@ int drt_gemm_nt_bf16_f32(const void* A, const void* B, float* C, int64_t m, int6
  * linear(FFN2, +bias +residual, fp32) -> layernorm).
  * ------------------------------------------------------------------------
  * drt_embed_ln: out[B*L, H] bf16 = LN(word_emb[ids] + type_emb[type_ids or 0]
- *   + pos_emb[l]) (modeling_bert.py:53-107); tables/LN params fp32, H % 256 == 0.
+ *   + pos_emb[l]) (modeling_bert.py:53-107); tables/LN params fp32, H % 256 == 0 or H == 384.
  * drt_linear_bf16: Y = X . W^T (+bias)(GELU)(+residual); X [M,K], W [N,K] bf16,
  *   bias fp32 [N] or NULL, residual bf16 [M,N] or NULL; flags bit0 = GELU(erf),
  *   bit1 = fp32 output (else bf16), bit3 = ReLU (after the bias, before the
@@ -352,6 +352,7 @@ int drt_gemm_nt_bf16_f32(const void* A, const void* B, float* C, int64_t m, int6
  * drt_layernorm_f32_bf16: out bf16 = LN(X fp32 [M,H]).
  * drt_layernorm_bf16: out bf16 = LN(X bf16 [M,H]) (fp32 statistics); the
  *   encoder's default, fed by a bf16 +bias +residual epilogue (one rounding).
+ *   Both: H % 256 == 0 or H == 384 (MiniLM-class towers), H <= 1024.
  * drt_attention_forward_bf16: the self-attention of a layer; "Attention" below.
  * drt_pool_bf16: reps fp32 [B,H] (+ optional bf16 copy) from hidden bf16
  *   [B,L,H]; mode 0 first, 1 masked mean, 2 max(hidden*mask) (utils.py:233-240).
@@ -590,7 +591,8 @@ int drt_l2_normalize_f32(float* x, int64_t B, int32_t H, void* out_bf16, void* s
  * ------------------------------------------------------------------------
  * drt_embed_ln_packed: out [T, H] bf16; packed row t of sequence b reads ids / type_ids (padded
  *   [B, L], type_ids may be NULL) at b * L + (t - cu[b]) and position row t - cu[b].  Each row has
- *   the bits of drt_embed_ln's row for the same token.  H % 256 == 0, H <= 1024, T <= B * L.
+ *   the bits of drt_embed_ln's row for the same token.  H % 256 == 0 or H == 384, H <= 1024,
+ *   T <= B * L.
  * drt_attention_varlen_forward_bf16: ctx [T, H] bf16 = softmax(Q K^T * scale) V per (sequence, head)
  *   from packed qkv [T, 3H], for the n_seqs sequences listed in seq_ids (int32, device; NULL =
  *   sequences 0 .. n_seqs - 1); rows of unlisted sequences are not touched.  Every listed sequence
@@ -615,6 +617,27 @@ int drt_pool_packed_bf16(const void* hidden, const int32_t* cu_seqlens, int64_t 
                          int32_t mode, float* out, void* out_bf16, void* stream);
 int drt_unpack_rows_bf16(const void* packed, const int32_t* cu_seqlens, int64_t B, int64_t L, int32_t H,
                          void* out, void* stream);
+/* ------------------------------------------------------------------------
+ * Attention at head_dim 32 (MiniLM-class towers: hidden 384, 12 heads), inference only: no lse, no
+ * dropout, no relative bias, no backward.  qkv [rows, 3H] bf16 (Q | K | V, head-major), ctx [rows, H]
+ * bf16, H = heads * 32; one work-group serves a pair of adjacent heads, so heads must be even.  Q is
+ * scaled as bf16(fp32 q * scale).  DRT_EINVAL before any HIP call for an odd or non-positive heads, L
+ * or max_len outside 1 .. 512, a NULL or not 16-byte aligned qkv / ctx, a NULL cu_seqlens; B == 0 or
+ * n_seqs == 0 is DRT_OK after the shape checks.
+ * ------------------------------------------------------------------------
+ * drt_attention_hd32_forward_bf16: the padded [B, L] rectangle, rows = B L.  mask int64 [B, L] or NULL
+ *   with the convention of drt_attention_forward_bf16: a masked key gets the finite -FLT_MAX, so a row
+ *   whose every key is masked is HF's uniform softmax over its L keys (no NaN).
+ * drt_attention_hd32_varlen_forward_bf16: a packed batch, cu_seqlens / seq_ids / max_len exactly as
+ *   drt_attention_varlen_forward_bf16: rows of unlisted sequences are not touched, a length above
+ *   max_len is clamped to it (the tail rows are not written), a length below 1 writes nothing; no
+ *   mask.  max_len sizes the LDS image and picks the launch shape, so the host may launch one length
+ *   class per call (model/packing.py plan.launches).                                              */
+int drt_attention_hd32_forward_bf16(const void* qkv, const int64_t* mask, void* ctx, int64_t B, int64_t L,
+                                    int32_t heads, float scale, void* stream);
+int drt_attention_hd32_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                           int64_t n_seqs, int32_t max_len, void* ctx, int32_t heads,
+                                           float scale, void* stream);
 /* ------------------------------------------------------------------------
  * Padding-free BERT training: the attention pair and the copies of a tower that runs on the packed
  * [T, H] rows (model/train_tower.py).  The first pair runs the whole-sequence kernels only:
