@@ -1,19 +1,18 @@
 // The attention forward kernel and its launcher (entries: csrc/encoder.hip, and
 // csrc/attention_varlen_long.hip for the packed training forward above 160 tokens).
 #pragma once
+#include "attention_tile.h"
 #include "drt_common.h"
 
 namespace drt {
 
 // ---------------------------------------------------------------------------
 // Attention.  One work-group (4 waves) per (sequence b, head hd); wave w owns
-// query blocks w, w+4, ... of 32 rows.  K is staged in LDS as swizzled
-// [key][8 x 16 B] rows (A operand of S^T = K Q^T), V transposed as Vt[d][key]
-// with a padded row stride (A operand of O^T = V^T P^T).
+// query blocks w, w+4, ... of 32 rows.  K, V^T and the key bias are staged in
+// the LDS image that attention_tile.h lays out (AttnLds), shared with the
+// head_dim-32 kernel.
 // ---------------------------------------------------------------------------
 constexpr int kAttnThreads = 256;
-constexpr int kHeadDim = 64;
-constexpr int kMaxSeq = 512;
 
 struct AttnArgs {
   const __bf16* qkv;      // [B*L][3*H]  (Q | K | V, head-major inside each)
@@ -48,17 +47,14 @@ struct AttnArgs {
 // wave loops over its query blocks and stores directly.
 // Round 3: scores in log2 units, s2 = fma(s, log2e, kb) with the key bias kb = 0 / -FLT_MAX (finite:
 // a row with every key masked gets HF's uniform softmax over its L keys, no NaN; the padding keys
-// L..Lp-1 get -inf, which key 0's finite score keeps out of any inf - inf); the running max moves only when a
-// tile's max exceeds it by more than kLazy (= 8, P <= 2^8 in bf16 / fp32 is exact to the same
-// relative precision), so the O rescale is a rare wave-uniform branch instead of 32 multiplies per
-// tile; dropout draws the keep decisions from the pairwise hash (drt_common.h), zeroes dropped P,
+// L..Lp-1 get -inf, which key 0's finite score keeps out of any inf - inf); the running max is
+// lazy (kLazy, attention_tile.h: why that is exact); dropout draws the keep decisions from the pairwise hash (drt_common.h), zeroes dropped P,
 // writes the keep words for the backward when asked (drop_bits), and moves 1 / (1 - p) into the
 // final 1 / l.  (Drawing the words in a separate one-thread-per-word pass for the forward to read
 // measured slower: 272 vs 178 us at 1024 x 128, profiles/r03r_attn_probe.log "bits" vs "hash".)
 // lse = (m + log2 l) ln 2 (natural log, what the backward rebuilds P from).
 // NW waves: 4, or 5 for 5 query blocks (129 <= L <= 160: the recipe's 156-token passages, the
 // reranker's 160-token pairs; with 4, wave 0 ran two blocks while three idled).
-constexpr float kLazy = 8.0f;
 constexpr float kLn2 = 0.6931471805599453f;
 
 // Register budget: 4 waves per SIMD (<= 128 VGPRs) -- at 5 query blocks the LDS (42 KiB) admits 3
@@ -97,13 +93,14 @@ void attention_fwd_kernel(AttnArgs a) {
     if (Lv <= 0) return;                    // the whole work-group: no barrier is left waiting
   }
   const int L = VL ? Lv : (int)a.L;
-  const int Lp = NB ? NB * 32 : (L + 31) & ~31;  // keys padded to the 32-key tile
+  const int Lp = NB ? NB * 32 : AttnLds::padded(L);  // keys padded to the 32-key tile
   const int nqb = Lp / 32;
-  const int vts = Lp * 2 + 8;              // Vt row stride (bytes): conflict-free ds_read_b64
-  char* Ks = smem;                          // Lp * 128 B
-  char* Vt = smem + Lp * 128;               // 64 * vts B
-  float* kb = (float*)(Vt + 64 * vts);      // Lp floats
-  float* rb = kb + Lp;                      // RB: 2 Lp floats
+  const AttnLds lds(Lp);
+  const int vts = lds.vts;
+  char* Ks = smem;
+  char* Vt = Ks + lds.ks_bytes;
+  float* kb = (float*)(Vt + lds.vt_bytes);
+  float* rb = (float*)((char*)kb + lds.kb_bytes);
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
@@ -291,20 +288,10 @@ void attention_fwd_kernel(AttnArgs a) {
       // O^T += V^T P^T over the 32 keys (2 k-steps of 16)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[8 * ks + j];
+        const bf16x8 pf = pv_fragment(s, ks);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          const char* vrow = Vt + (t ? offV1 : offV0) + (kt + 16 * ks) * 2;
-          const bf16x4 v0 = *(const bf16x4*)(vrow);
-          const bf16x4 v1 = *(const bf16x4*)(vrow + 16);
-          bf16x8 vf;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vf[j] = v0[j];
-            vf[4 + j] = v1[j];
-          }
+          const bf16x8 vf = vt_operand(Vt + (t ? offV1 : offV0) + (kt + 16 * ks) * 2);
           o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[t], 0, 0, 0);
         }
       }
@@ -374,20 +361,15 @@ void attention_fwd_kernel(AttnArgs a) {
 }
 
 // Launch of attention_fwd_kernel for sequences of at most `len` tokens (L, or a varlen launch's
-// max_len), one work-group per (sequence, head) group: the one place that knows the length class NB,
-// the LDS image (K rows, V^T, key bias, and the staged relative bias with `rb`) and the block size.
-// `pick(NB)` names the caller's instantiation of the class (NB = 0: len > 160), so a new
-// instantiation is one more entry in its caller's table and no launch code.
+// max_len), one work-group per (sequence, head) group: the one place that knows the length class NB
+// and its block size (the LDS image and its opt-in: launch_attention_lds).  `pick(NB)` names the
+// caller's instantiation of the class (NB = 0: len > 160), so a new instantiation is one more entry
+// in its caller's table and no launch code.
 template <typename Pick>
 static int launch_attention_fwd(Pick&& pick, AttnArgs& a, int len, bool rb, int64_t groups, void* stream) {
-  const int Lp = (len + 31) & ~31;
-  const int nb = Lp / 32 <= 5 ? Lp / 32 : 0;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4 + (rb ? (size_t)Lp * 8 : 0);
-  const void* kernel = (const void*)pick(nb);
-  if (lds > kDefaultLdsBytes) DRT_CHECK_HIP(allow_large_lds(kernel));   // len > 224 (NB = 0 only)
-  void* args[] = {&a};
-  hipLaunchKernel(kernel, dim3((unsigned)groups), dim3(nb == 5 ? 320 : 256), args, lds, (hipStream_t)stream);
-  return hip_status(hipGetLastError());
+  const int nqb = AttnLds::padded(len) / 32;
+  const int nb = nqb <= 5 ? nqb : 0;
+  return launch_attention_lds((const void*)pick(nb), a, len, rb, groups, nb == 5 ? 320 : 256, stream);
 }
 
 // The checked arguments of the two varlen training forwards (drt_attention_varlen_train_forward_bf16 and

@@ -7,7 +7,8 @@
 // of work is a PAIR of adjacent heads: one work-group per (sequence, head pair) reads 128 contiguous
 // bytes per token and matrix -- the 64-wide kernel's 8 x 16-B chunk loads, its swizzled K rows
 // ([key][8 x 16 B], chunks 0..3 head A's d 0..31, chunks 4..7 head B's) and its V^T image (Vt[d][key],
-// rows 0..31 head A, 32..63 head B), hence its LDS size: 128 Lp + 64 (2 Lp + 8) + 4 Lp bytes.
+// rows 0..31 head A, 32..63 head B), hence its LDS image and launch: AttnLds and launch_attention_lds
+// (attention_tile.h).
 //
 // Products: v_mfma_f32_32x32x16_bf16 for both.  S^T = K Q^T of a 32-key x 32-query tile is two k-steps
 // (d = 32) into one accumulator whose lane holds its query's scores, and that accumulator, converted
@@ -25,19 +26,19 @@
 // two heads as two independent chains in one loop body, 126 VGPRs, 4 waves per SIMD -- tied at
 // 512 x 128 and lost 4 to 9 % at 512 x 32, 256 x 160 and 64 x 512, and is gone.
 //
+// Shared with the 64-wide kernel through attention_tile.h: the LDS plan, the launch, kLazy / kMaxSeq and the
+// operands of the P V k-step (pv_fragment, vt_operand).  The staging pass, the key-bias fill, the varlen
+// prologue and the softmax tile below are still that kernel's text, copied: a change to one belongs in both.
 // Kept from the 64-wide kernel: the online softmax in log2 units with the lazy rescale (kLazy), the
 // key bias kb = 0 / -FLT_MAX (masked: finite, so a row of masked keys is HF's uniform softmax) / -inf
 // (tile padding), non-temporal K / V loads, Q scaled as bf16(fp32 q * scale), 16-B ctx stores: the
 // two lane halves of an O^T accumulator hold the two 8-B halves of each 16-B piece of a query's row,
 // so they trade one half each (a cross-half shuffle) and every lane stores two whole 16-B pieces: a
 // head's 64-B row leaves in two consecutive instructions of one wave.
+#include "attention_tile.h"
 #include "drt_common.h"
 
 namespace drt {
-
-constexpr int kHd32 = 32;
-constexpr int kHd32MaxSeq = 512;
-constexpr float kHd32Lazy = 8.0f;   // the 64-wide kernel's kLazy
 
 struct Attn32Args {
   const __bf16* qkv;          // [rows][3 H]  (Q | K | V, head-major inside each)
@@ -65,12 +66,13 @@ void attention_hd32_kernel(Attn32Args a) {
     L = L < a.max_len ? L : a.max_len;
     if (L <= 0) return;                     // the whole work-group: no barrier is left waiting
   }
-  const int Lp = (L + 31) & ~31;            // keys padded to the 32-key tile
+  const int Lp = AttnLds::padded(L);        // keys padded to the 32-key tile
   const int nqb = Lp >> 5;
-  const int vts = Lp * 2 + 8;               // Vt row stride (bytes): conflict-free ds_read_b64
-  char* Ks = smem;                          // Lp * 128 B
-  char* Vt = smem + Lp * 128;               // 64 * vts B
-  float* kb = (float*)(Vt + 64 * vts);      // Lp floats
+  const AttnLds lds(Lp);
+  const int vts = lds.vts;
+  char* Ks = smem;
+  char* Vt = Ks + lds.ks_bytes;
+  float* kb = (float*)(Vt + lds.vt_bytes);
 
   const int tid = threadIdx.x, NT = blockDim.x;
   const int wave = tid >> 6, lane = tid & 63;
@@ -175,7 +177,7 @@ void attention_hd32_kernel(Attn32Args a) {
         mt = fmaxf(fmaxf(mt, fmaxf(lo[0], lo[1])), fmaxf(hi[0], hi[1]));
       }
       mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const bool grow = mt > m + kHd32Lazy;
+      const bool grow = mt > m + kLazy;
       if (__builtin_amdgcn_ballot_w64(grow) != 0ull) {   // rare after the first tile
         const float mn = grow ? mt : m;
         const float alpha = __builtin_amdgcn_exp2f(m - mn);
@@ -202,19 +204,8 @@ void attention_hd32_kernel(Attn32Args a) {
       // order of the S^T accumulator (keys 16 ks + 4 h + {0..3} and + 8)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[8 * ks + j];
-        const char* vrow = Vt + offV + (kt + 16 * ks) * 2;
-        const bf16x4 v0 = *(const bf16x4*)(vrow);
-        const bf16x4 v1 = *(const bf16x4*)(vrow + 16);
-        bf16x8 vf;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          vf[j] = v0[j];
-          vf[4 + j] = v1[j];
-        }
-        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o, 0, 0, 0);
+        const bf16x8 pf = pv_fragment(s, ks);
+        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt_operand(Vt + offV + (kt + 16 * ks) * 2), pf, o, 0, 0, 0);
       }
     }
 
@@ -249,14 +240,9 @@ void attention_hd32_kernel(Attn32Args a) {
 // LDS image and picks the wave count: 4 (two query-block slots per head), or 6 at 3 or 5 query blocks.
 template <bool VL>
 static int launch_attention_hd32(Attn32Args& a, int len, int64_t groups, void* stream) {
-  const int Lp = (len + 31) & ~31, nqb = Lp / 32;
-  const size_t lds = (size_t)Lp * 128 + (size_t)64 * (Lp * 2 + 8) + (size_t)Lp * 4;
+  const int nqb = AttnLds::padded(len) / 32;
   const int waves = nqb == 3 || nqb == 5 ? 6 : 4;
-  const void* kernel = (const void*)attention_hd32_kernel<VL>;
-  if (lds > kDefaultLdsBytes) DRT_CHECK_HIP(allow_large_lds(kernel));   // len > 224
-  void* args[] = {&a};
-  (void)hipLaunchKernel(kernel, dim3((unsigned)groups), dim3(waves * 64), args, lds, (hipStream_t)stream);
-  return hip_status(hipGetLastError());
+  return launch_attention_lds((const void*)attention_hd32_kernel<VL>, a, len, false, groups, waves * 64, stream);
 }
 
 }  // namespace drt
@@ -267,7 +253,7 @@ extern "C" {
 
 int drt_attention_hd32_forward_bf16(const void* qkv, const int64_t* mask, void* ctx, int64_t B, int64_t L,
                                     int32_t heads, float scale, void* stream) {
-  DRT_REQUIRE(B >= 0 && L > 0 && L <= kHd32MaxSeq && heads > 0 && heads % 2 == 0);
+  DRT_REQUIRE(B >= 0 && L > 0 && L <= kMaxSeq && heads > 0 && heads % 2 == 0);
   DRT_REQUIRE(B * (heads / 2) < (1ll << 31));
   if (B == 0) return DRT_OK;
   DRT_REQUIRE(qkv && ctx && (uintptr_t)qkv % 16 == 0 && (uintptr_t)ctx % 16 == 0);
@@ -278,7 +264,7 @@ int drt_attention_hd32_forward_bf16(const void* qkv, const int64_t* mask, void* 
 int drt_attention_hd32_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
                                            int64_t n_seqs, int32_t max_len, void* ctx, int32_t heads, float scale,
                                            void* stream) {
-  DRT_REQUIRE(n_seqs >= 0 && max_len > 0 && max_len <= kHd32MaxSeq && heads > 0 && heads % 2 == 0);
+  DRT_REQUIRE(n_seqs >= 0 && max_len > 0 && max_len <= kMaxSeq && heads > 0 && heads % 2 == 0);
   DRT_REQUIRE(n_seqs * (heads / 2) < (1ll << 31));
   if (n_seqs == 0) return DRT_OK;
   DRT_REQUIRE(qkv && cu_seqlens && ctx && (uintptr_t)qkv % 16 == 0 && (uintptr_t)ctx % 16 == 0);

@@ -57,7 +57,7 @@ def _check_supported(shape: BertShape):
         raise ValueError("head_dim must be 64")
     if shape.intermediate % 64:
         raise ValueError("intermediate size must be a multiple of 64")
-    if shape.act not in ("gelu", "gelu_new") and shape.act != "gelu":
+    if shape.act not in ("gelu", "gelu_new"):
         raise ValueError(f"activation {shape.act} unsupported (erf GELU only)")
     if shape.act != "gelu":
         raise ValueError("only erf GELU ('gelu') is implemented")
@@ -316,26 +316,29 @@ class HipBertEncoder:
         dh = H // sh.heads
         scale = 1.0 / math.sqrt(dh)
         mp = mask.data_ptr() if mask is not None else None
+        q, c, lib, st = qkv.data_ptr(), ctx.data_ptr(), self.lib, self.stream
+        # the attention entry by head_dim, padded or packed, and its calls: the same for every layer
+        if plan is None and dh == 32:
+            name, calls = "drt_attention_hd32_forward_bf16", [(q, mp, c, B, L, sh.heads, scale, st)]
+        elif plan is None:
+            name = "drt_attention_forward_bf16"
+            calls = [(q, mp, None, c, None, None, B, L, sh.heads, dh, scale, 0.0, 0, 0, st)]
+        elif dh == 32:
+            name = "drt_attention_hd32_varlen_forward_bf16"
+            calls = [(q, cu, sp, n, ml, c, sh.heads, scale, st) for sp, n, ml in launches]
+        else:
+            name = "drt_attention_varlen_forward_bf16"
+            calls = [(q, cu, sp, n, ml, c, sh.heads, dh, scale, st) for sp, n, ml in launches]
+
+        entry = getattr(lib, name)
+
+        def attend():
+            for args in calls:
+                _native.check(entry(*args), name)
+
         for ly in self.layers:
             self._lin(h, ly["wqkv"], ly["bqkv"], qkv)
-            if plan is None and dh == 32:
-                _native.check(self.lib.drt_attention_hd32_forward_bf16(qkv.data_ptr(), mp, ctx.data_ptr(), B, L,
-                                                                       sh.heads, scale, self.stream),
-                              "drt_attention_hd32_forward_bf16")
-            elif plan is None:
-                _native.check(self.lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, None, ctx.data_ptr(), None, None,
-                                                                  B, L, sh.heads, dh, scale, 0.0, 0, 0,
-                                                                  self.stream), "drt_attention_forward_bf16")
-            elif dh == 32:
-                for sp, n, ml in launches:
-                    _native.check(self.lib.drt_attention_hd32_varlen_forward_bf16(
-                        qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(), sh.heads, scale, self.stream),
-                        "drt_attention_hd32_varlen_forward_bf16")
-            else:
-                for sp, n, ml in launches:
-                    _native.check(self.lib.drt_attention_varlen_forward_bf16(
-                        qkv.data_ptr(), cu, sp, n, ml, ctx.data_ptr(), sh.heads, dh, scale, self.stream),
-                        "drt_attention_varlen_forward_bf16")
+            attend()
             self._lin_ln(ctx, ly["wo"], ly["bo"], h, ly["g1"], ly["b1"], x32, ln)
             self._lin(h, ly["wi"], ly["bi"], ffn, gelu=True)
             self._lin_ln(ffn, ly["wf"], ly["bf"], h, ly["g2"], ly["b2"], x32, ln)

@@ -65,6 +65,20 @@ for classes in (False, True):
     dig(f"unpack classes={classes}", enc.unpack(hid, plan, L))
 enc.packed_classes = False
 
+# MiniLM-class tower (hidden 384, 12 heads of 32): the head_dim-32 attention, padded and packed, same batches
+torch.manual_seed(3)
+mini = BertModel(BertConfig(vocab_size=1000, hidden_size=384, num_hidden_layers=2, num_attention_heads=12,
+                            intermediate_size=1536, max_position_embeddings=512), add_pooling_layer=False).to(dev).eval()
+menc = HipBertEncoder.from_hf(mini, dev)
+for B, L, lens in ((4, 40, [40, 7, 33, 1]), (3, 160, [160, 129, 5]), (2, 200, [200, 61])):
+    ids, mask = batch(B, L, lens, 10 + B)
+    dig(f"minilm forward[{B},{L}]", menc(ids, mask))
+lens, L = [5, 1, 32, 17, 40], 40
+ids, mask = batch(5, L, lens, 20)
+for classes in (False, True):
+    menc.packed_classes = classes
+    dig(f"minilm forward_packed classes={classes}", menc.forward_packed(ids, plan_packing(mask, L, device=dev, min_saving=0.0)))
+
 ids, mask = batch(4, 40, [40, 7, 33, 1], 14)
 enc.split_min_tokens = 64
 dig("forward[4,40] two streams", enc(ids, mask))
