@@ -145,6 +145,8 @@ _SIGNATURES = [
     ("drt_embed_ln_packed", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32,
                                     c_vp, c_vp]),
     ("drt_attention_varlen_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_f32, c_vp]),
+    ("drt_attention_varlen_relbias_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32,
+                                                          c_i32, c_f32, c_vp]),
     ("drt_attention_hd32_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, c_vp]),
     ("drt_attention_hd32_varlen_forward_bf16", c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_f32, c_vp]),
     ("drt_pool_packed_bf16", c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),

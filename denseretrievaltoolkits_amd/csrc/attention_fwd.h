@@ -37,6 +37,9 @@ struct AttnArgs {
   // (row cu[b] + q of head h), and the keep hash takes the padded batch's row (b * heads + h) * L_pad + q
   int64_t L_pad, T;
   int W;
+  // RB x VL (drt_attention_varlen_relbias_forward_bf16): relbias is ONE centred table [heads][2 S - 1],
+  // S = bias_len >= max_len; entry (head, key - query + S - 1) serves every sequence of the batch
+  int bias_len;
 };
 
 // Attention forward, one work-group per (sequence, head): K (swizzled rows), V^T and the key bias
@@ -78,6 +81,13 @@ constexpr float kLn2 = 0.6931471805599453f;
 // keep words are stored tile by tile, the first ceil(len / 32) of its W.  That form
 // is instantiated in csrc/attention_varlen_long.hip, which is compiled without the packed FP32
 // instructions; two scalar operations round as one packed one does.
+// RB x VL = 1 (packed T5 towers, drt_attention_varlen_relbias_forward_bf16): the bucket of a bias depends
+// on key - query alone, so one centred table of a fixed span S (AttnArgs::bias_len) serves every
+// sequence, length class and batch.  A work-group stages the 2 len - 1 entries its sequence can reach
+// into the same rb image (sized by the launch's max_len, zero tail); the per-query read and the tile
+// body are the padded RB form's, so a sequence of n tokens gets the ctx bits of the padded kernel at
+// B = 1, L = n with the L = n table.  Instantiated in csrc/encoder.hip only (packed FP32 on, as the
+// padded RB kernels).
 template <int NB, bool DROP, bool RB = false, int VL = 0>
 __global__ __launch_bounds__(NB == 5 ? 320 : 256) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void attention_fwd_kernel(AttnArgs a) {
@@ -164,7 +174,11 @@ void attention_fwd_kernel(AttnArgs a) {
     kb[i] = bv;
   }
   if (RB) {
-    const float* src = a.relbias + (int64_t)hd * (2 * L - 1);
+    // entry i of the image: the bias of key - query = i - (L - 1).  Padded: the head's [2 L - 1] table whole.
+    // VL: the window of the head's centred span-S table that this sequence reaches, entries S - L ..
+    // S + L - 2 (L <= max_len <= S, so the window never leaves the head's row)
+    const float* src = VL ? a.relbias + (int64_t)hd * (2 * a.bias_len - 1) + (a.bias_len - L)
+                          : a.relbias + (int64_t)hd * (2 * L - 1);
     for (int i = tid; i < 2 * Lp; i += NT) rb[i] = i < 2 * L - 1 ? src[i] * kLog2e : 0.0f;
   }
   __syncthreads();

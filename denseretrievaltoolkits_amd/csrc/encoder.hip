@@ -13,7 +13,9 @@
 //                   relative-position bias to the scores (drt_attention_forward_bf16, relbias);
 //                   the VL instantiations read each sequence's rows from a sequence-offset
 //                   table (packed batches, drt_attention_varlen_forward_bf16; csrc/packed.hip), with
-//                   lse and dropout for training (drt_attention_varlen_train_forward_bf16)
+//                   lse and dropout for training (drt_attention_varlen_train_forward_bf16), or with
+//                   the bias window of one span-S table (packed T5 towers,
+//                   drt_attention_varlen_relbias_forward_bf16)
 //   pool            first / masked-mean / masked-max pooling (utils.py:233-240)
 //   l2norm          F.normalize(reps, dim=1) (biencoder.py:149-150)
 #include "attention_fwd.h"
@@ -361,6 +363,27 @@ int drt_attention_varlen_forward_bf16(const void* qkv, const int32_t* cu_seqlens
       attention_fwd_kernel<2, false, false, 1>, attention_fwd_kernel<3, false, false, 1>,
       attention_fwd_kernel<4, false, false, 1>, attention_fwd_kernel<5, false, false, 1>};
   return launch_attention_fwd([&](int nb) { return kernels[nb]; }, a, max_len, false, n_seqs * heads, stream);
+}
+
+// The forward over a packed batch with T5's relative-position bias (contract: drt.h): the RB x VL
+// instantiations.  relbias is the tower's one centred table of span bias_len; a work-group stages its
+// sequence's window of it (attention_fwd.h), so the LDS image carries the rb region of max_len keys.
+int drt_attention_varlen_relbias_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                              int64_t n_seqs, int32_t max_len, const float* relbias, int32_t bias_len,
+                                              void* ctx, int32_t heads, int32_t head_dim, float scale, void* stream) {
+  DRT_REQUIRE(n_seqs >= 0 && max_len > 0 && max_len <= kMaxSeq && heads > 0 && head_dim == kHeadDim);
+  DRT_REQUIRE(bias_len >= max_len && bias_len <= kMaxSeq);
+  DRT_REQUIRE(n_seqs * heads < (1ll << 31));
+  if (n_seqs == 0) return DRT_OK;
+  DRT_REQUIRE(qkv && cu_seqlens && relbias && ctx);
+  AttnArgs a{(const __bf16*)qkv, nullptr, (__bf16*)ctx, 0, 0, heads, heads * head_dim, scale, nullptr, 0.0f, 0, 0,
+             nullptr, relbias, cu_seqlens, seq_ids, max_len, 0, 0, 0, bias_len};
+  using Kernel = void (*)(AttnArgs);
+  static constexpr Kernel kernels[6] = {
+      attention_fwd_kernel<0, false, true, 1>, attention_fwd_kernel<1, false, true, 1>,
+      attention_fwd_kernel<2, false, true, 1>, attention_fwd_kernel<3, false, true, 1>,
+      attention_fwd_kernel<4, false, true, 1>, attention_fwd_kernel<5, false, true, 1>};
+  return launch_attention_fwd([&](int nb) { return kernels[nb]; }, a, max_len, true, n_seqs * heads, stream);
 }
 
 // The training forward over a packed batch (contract: drt.h): VL x {plain, DROP} at the five

@@ -14,6 +14,8 @@ biencoder.py:159-241).  What changes is where the arithmetic runs:
   tokens of a padded batch (model/packing.py, HipBertEncoder.forward_packed): ``reps`` as
   before, ``hidden`` [B, L, H] with ZEROS at the pad positions.  A mask that is not a batch of
   non-empty prefixes, a batch with too little padding and T5 towers keep the padded path.
+  ``hip_packed_t5 = True`` (attribute, or ``model_args.hip_packed_t5``; default off) is the same
+  switch for T5EncoderModel towers (HipT5Encoder.forward_packed), with the same thresholds.
 * encode with autograd (training, or eval mode with grad on, where the reference
   returns differentiable reps) runs BERT towers up to L = 512 on the HIP training
   tower (model/train_tower.py: forward with saved bf16 activations + backward on
@@ -80,17 +82,21 @@ def _log_fallback(why: str):
         logger.warning("DRModel.encode: HF module under torch, not the HIP tower (%s)", why)
 
 
-def packed_plan(enc, items):
+def packed_plan(enc, items, t5=False):
     """The packing plan of a batch for an encode with ``hip_packed`` set, or None (padded path, the
     reason logged once): the tower is not a HipBertEncoder (T5 stays padded), or the mask is not a
-    batch of non-empty prefixes with padding to drop (model/packing.py)."""
-    if not isinstance(enc, HipBertEncoder):
+    batch of non-empty prefixes with padding to drop (model/packing.py).  ``t5``: the caller's
+    ``hip_packed_t5`` is set -- a HipT5Encoder is planned too, with the same thresholds."""
+    flag = "hip_packed"
+    if t5 and isinstance(enc, HipT5Encoder):
+        flag = "hip_packed_t5"
+    elif not isinstance(enc, HipBertEncoder):
         _log_fallback(f"hip_packed: padded path, {type(enc).__name__} has no packed form")
         return None
     ids = items["input_ids"]
     plan = plan_packing(items.get("attention_mask"), ids.shape[1], device=enc.device)
     if plan is None or plan.B != ids.shape[0]:
-        _log_fallback("hip_packed: padded path, the mask is not a batch of non-empty prefixes with "
+        _log_fallback(f"{flag}: padded path, the mask is not a batch of non-empty prefixes with "
                       "enough padding to drop")
         return None
     return plan
@@ -145,6 +151,9 @@ class DRModel(nn.Module):
         # opt-in: padding-free inference of BERT towers (only the real tokens of a padded batch are
         # computed; model/packing.py, HipBertEncoder.forward_packed)
         self.hip_packed = bool(getattr(model_args, "hip_packed", False))
+        # opt-in: the same for T5EncoderModel towers (HipT5Encoder.forward_packed: the varlen attention
+        # with the relative-position bias).  Its own switch: hip_packed alone keeps T5 padded
+        self.hip_packed_t5 = bool(getattr(model_args, "hip_packed_t5", False))
         # opt-in: padding-free TRAINING of BERT towers (the autograd pass of train_hidden on the packed
         # rows; model/train_tower.py).  Separate from hip_packed, which covers the no-grad encode only.
         self.hip_packed_train = bool(getattr(model_args, "hip_packed_train", False))
@@ -266,7 +275,10 @@ class DRModel(nn.Module):
         # it takes the HF module below, with the reason logged, whether or not autograd is on
         if self._use_hip(model) and self.feature == "last_hidden_state":
             enc = self._hip_encoder(model)
-            plan = packed_plan(enc, items) if self.hip_packed else None
+            if self.hip_packed_t5 and isinstance(enc, HipT5Encoder):
+                plan = packed_plan(enc, items, t5=True)
+            else:
+                plan = packed_plan(enc, items) if self.hip_packed else None
             if plan is not None:
                 # padding-free: only the real tokens are computed; `hidden` comes back in the padded
                 # [B, L, H] layout with ZEROS at the pad positions (the padded path leaves the

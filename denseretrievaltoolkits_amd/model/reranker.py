@@ -16,7 +16,9 @@ scores = ``logits[:, 0, [neg_token_id, pos_token_id]]``) follow the same rule: w
 ask for, the encoder runs on ``HipT5Encoder`` and the single decoder step on the absorbed
 cross-attention kernels (model/t5_decoder.py, ``HipT5PairScorer``), returning [B, 2] fp32 in the
 reference's column order; with grad on, or on the CPU, the HF module computes exactly what the
-reference computes.  A configuration the kernels do not cover raises ``NotImplementedError`` on the
+reference computes.  ``hip_packed_t5 = True`` (attribute, or ``model_args.hip_packed_t5``; default off)
+runs that encoder on the pairs' real tokens only and unpacks its output for the decoder step
+(``hip_packed`` alone keeps a T5 reranker padded).  A configuration the kernels do not cover raises ``NotImplementedError`` on the
 no-grad GPU path.
 """
 from __future__ import annotations
@@ -77,6 +79,9 @@ class RRModel(nn.Module):
         self._hip = None
         # opt-in: padding-free inference of a BERT pair tower (model/packing.py); T5 rerankers stay padded
         self.hip_packed = bool(getattr(model_args, "hip_packed", False))
+        # opt-in: a T5 reranker's ENCODER runs padding-free (HipT5Encoder.forward_packed); its output is
+        # unpacked for the one-step decoder, whose cross-attention masks the pad keys
+        self.hip_packed_t5 = bool(getattr(model_args, "hip_packed_t5", False))
         # opt-in: padding-free training of a BERT pair tower (model/train_tower.py); separate from hip_packed
         self.hip_packed_train = bool(getattr(model_args, "hip_packed_train", False))
         # opt-in, with hip_packed_train: pairs of 161 .. 512 tokens train packed too (default: padded tower)
@@ -129,7 +134,12 @@ class RRModel(nn.Module):
         tokens = (self.neg_token_id, self.pos_token_id)
         frozen = not any(p.requires_grad for p in self.lm.parameters())
         if dev.type == "cuda" and (not torch.is_grad_enabled() or frozen):
-            return self._hip_t5_state().logits(items["input_ids"], items.get("attention_mask"), tokens)
+            scorer = self._hip_t5_state()
+            plan = None
+            if self.hip_packed_t5:    # padding-free encoder: the pairs' real tokens only, then unpacked
+                from .biencoder import packed_plan
+                plan = packed_plan(scorer.encoder, items, t5=True)
+            return scorer.logits(items["input_ids"], items.get("attention_mask"), tokens, plan=plan)
         from .biencoder import _log_fallback
         _log_fallback("T5 reranker: " + ("tower on the CPU" if dev.type != "cuda" else
                                          "autograd on (the decoder step has no HIP backward)"))
@@ -143,7 +153,7 @@ class RRModel(nn.Module):
             return None, None
         items = BatchEncoding(items)
         if "T5" in type(self.lm).__name__ and not getattr(self.model_args, "encoder_only", False):
-            if self.hip_packed:
+            if self.hip_packed and not self.hip_packed_t5:
                 from .biencoder import _log_fallback
                 _log_fallback("hip_packed: padded path, a T5 reranker has no packed form")
             if self.hip_packed_train and torch.is_grad_enabled():

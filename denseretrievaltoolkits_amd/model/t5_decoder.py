@@ -203,9 +203,14 @@ class HipT5PairScorer:
             h, h2 = h2, h
         return self._rms(h, self.final_g, x)
 
-    def _encode(self, input_ids, attention_mask):
+    def _encode(self, input_ids, attention_mask, plan=None):
+        """The encoder output [B, L, D] and the mask.  With ``plan`` (model/packing.py) the encoder runs on
+        the pairs' real tokens only and its output is unpacked: zeros at the pad positions, which the
+        cross-attention's key mask keeps out of the step."""
         dev = self.device
         mask = attention_mask.to(dev, torch.int64).contiguous() if attention_mask is not None else None
+        if plan is not None:
+            return self.encoder.unpack(self.encoder.forward_packed(input_ids, plan), plan, input_ids.shape[1]), mask
         enc = self.encoder(input_ids, mask).contiguous()
         return enc, mask
 
@@ -215,10 +220,11 @@ class HipT5PairScorer:
         return self._decode(enc, mask)
 
     def logits(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
-               token_ids: Sequence[int]) -> torch.Tensor:
-        """HF logits[:, 0, token_ids] for decoder_input_ids = 0: [B, len(token_ids)] fp32."""
+               token_ids: Sequence[int], plan=None) -> torch.Tensor:
+        """HF logits[:, 0, token_ids] for decoder_input_ids = 0: [B, len(token_ids)] fp32.  ``plan``: the
+        batch's packing plan, for a padding-free encoder pass (the decoder step is unchanged)."""
         rows = self._rows(token_ids)
-        enc, mask = self._encode(input_ids, attention_mask)
+        enc, mask = self._encode(input_ids, attention_mask, plan)
         y = self._decode(enc, mask, n_tokens=rows.shape[0])
         out = torch.empty((y.shape[0], rows.shape[0]), dtype=torch.float32, device=self.device)
         return self._lin(y, rows, out, flags=LIN_F32)

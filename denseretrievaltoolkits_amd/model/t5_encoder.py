@@ -16,7 +16,9 @@ towers (transformers modeling_t5.py, eval mode) for inference:
     h = rmsnorm(h, final_layer_norm)
 
 The relative-position bias of block 0 serves every block; it reaches the attention kernel as a
-table over k - q (``relative_bias_table``), built once per sequence length.  Weights are
+table over k - q (``relative_bias_table``), built once per sequence length; the padding-free form
+(``forward_packed``, the plan of model/packing.py) computes the real tokens only and reads every
+sequence's window of ONE table of span ``MAX_SEQ``.  Weights are
 snapshotted from the HF module (bf16 linears, fp32 embedding / norm weights / bias table).
 """
 from __future__ import annotations
@@ -101,6 +103,10 @@ class HipT5Encoder:
             raise ValueError(why)
         self.split_streams = True       # two halves on two streams, as HipBertEncoder
         self.split_min_tokens = 8192
+        # forward_packed switches, HipBertEncoder's: one attention launch per length class of the plan
+        # (else one per batch), and two packed halves on two streams from split_min_tokens real tokens up
+        self.packed_classes = False
+        self.packed_split_streams = False
         self._streams = None
         self._ws_plan = {}
         self._ws = None
@@ -198,7 +204,10 @@ class HipT5Encoder:
                                                   (part(half, B), slice(half * L, B * L))]).view(B, L, -1)
         return self._run(ids, mask)
 
-    def _run(self, ids, mask, out=None):
+    def _run(self, ids, mask, out=None, plan=None):
+        """The layer loop.  Padded: ``[B, L, D]`` over the rectangle with the ``L`` bias table.  With ``plan``
+        (model/packing.py): ``ids`` are the plan's T real ids as ``[1, T]``, attention is the varlen
+        relative-bias entry over the span-``MAX_SEQ`` table, one call per launch of the plan; ``[1, T, D]``."""
         sh = self.shape
         dev = self.device
         lib = self.lib
@@ -206,7 +215,7 @@ class HipT5Encoder:
         D, I, F, T = sh.d_model, sh.heads * sh.d_kv, sh.d_ff, B * L
         gated = sh.act == "gated-gelu"
         self.stream = _native.stream_ptr(dev)
-        table = self._bias_table(L)
+        table = self._bias_table(L if plan is None else MAX_SEQ)
 
         def buf(n):
             return torch.empty((T, n), dtype=torch.bfloat16, device=dev)
@@ -219,12 +228,22 @@ class HipT5Encoder:
         _native.check(lib.drt_t5_embed_bf16(ids.data_ptr(), B, L, self.word.data_ptr(), D, h.data_ptr(), self.stream),
                       "drt_t5_embed_bf16")
         mp = mask.data_ptr() if mask is not None else None
+        q, c, tp, st = qkv.data_ptr(), ctx.data_ptr(), table.data_ptr(), self.stream
+        # the attention entry, padded or packed, and its calls: the same for every layer
+        if plan is None:
+            name = "drt_attention_forward_bf16"
+            calls = [(q, mp, tp, c, None, None, B, L, sh.heads, sh.d_kv, 1.0, 0.0, 0, 0, st)]
+        else:
+            name = "drt_attention_varlen_relbias_forward_bf16"
+            cu = plan.cu_seqlens.data_ptr()
+            calls = [(q, cu, sp, n, ml, tp, MAX_SEQ, c, sh.heads, sh.d_kv, 1.0, st)
+                     for sp, n, ml in plan.launches(self.packed_classes)]
+        entry = getattr(lib, name)
         for ly in self.layers:
             self._rms(h, ly["g0"], x)
             self._lin(x, ly["wqkv"], qkv)
-            _native.check(lib.drt_attention_forward_bf16(qkv.data_ptr(), mp, table.data_ptr(), ctx.data_ptr(), None, None,
-                                                         B, L, sh.heads, sh.d_kv, 1.0, 0.0, 0, 0, self.stream),
-                          "drt_attention_forward_bf16")
+            for args in calls:
+                _native.check(entry(*args), name)
             self._lin(ctx, ly["wo"], h2, resid=h)
             self._rms(h2, ly["g1"], x)
             if gated:
@@ -240,3 +259,42 @@ class HipT5Encoder:
     __call__ = forward
 
     pool = HipBertEncoder.pool          # drt_pool_bf16 with the reference's pooling semantics
+
+    # -- padding-free inference ---------------------------------------------
+    # Only the T real tokens of the batch are computed (model/packing.py).  T5 has no position table, so
+    # the packed embedding is drt_t5_embed_bf16 over the gathered real ids; RMSNorm, the linears and the
+    # gate take M = T rows; the attention reads each sequence's window of ONE span-MAX_SEQ bias table.
+    def forward_packed(self, input_ids: torch.Tensor, plan, token_type_ids: Optional[torch.Tensor] = None
+                       ) -> torch.Tensor:
+        """last_hidden_state of the real tokens, [T, d_model] bf16 in the plan's packed order."""
+        if token_type_ids is not None:
+            raise ValueError("T5 has no token types: token_type_ids must be None")
+        dev = self.device
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        B, L = ids.shape
+        if (B, L) != (plan.B, plan.L):
+            raise ValueError(f"plan of a [{plan.B}, {plan.L}] batch used with input_ids [{B}, {L}]")
+        if L > MAX_SEQ:
+            raise ValueError(f"sequence length {L} exceeds the attention kernel's {MAX_SEQ}")
+        # packed row t is token (b, t - cu[b]) with b the sequence whose rows hold t: index arithmetic on
+        # the device from the plan's table, no copy to the host
+        cu = plan.cu_seqlens.to(torch.int64)
+        t = torch.arange(plan.T, device=dev)
+        b = torch.searchsorted(cu[1:], t, right=True)
+        real = ids.view(-1)[b * L + (t - cu[b])].view(1, plan.T)
+        self._bias_table(MAX_SEQ)           # built once, on the launch stream, before any fork
+        if (self.packed_split_streams and B >= 2 and plan.T >= self.split_min_tokens
+                and not torch.cuda.is_current_stream_capturing()):
+            def part(r0, sub):
+                return lambda out: self._run(real[:, r0:r0 + sub.T], None, out=out, plan=sub)
+
+            parts, row = [], 0
+            for _, sub in plan.halves():
+                parts.append((part(row, sub), slice(row, row + sub.T)))
+                row += sub.T
+            out = torch.empty((plan.T, self.shape.d_model), dtype=torch.bfloat16, device=dev)
+            return run_on_two_streams(self, out, parts)
+        return self._run(real, None, plan=plan).view(plan.T, -1)
+
+    pool_packed = HipBertEncoder.pool_packed    # drt_pool_packed_bf16: max pooling sees a 0 at every pad
+    unpack = HipBertEncoder.unpack              # [B, L, D] with zeros at the pad positions

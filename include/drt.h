@@ -734,6 +734,25 @@ int drt_t5_embed_bf16(const int64_t* ids, int64_t B, int64_t L, const float* tab
 int drt_rmsnorm_bf16(const void* X, int64_t M, int32_t H, const float* weight, float eps,
                      void* out, void* stream);
 int drt_gated_gelu_new_bf16(const void* X, int64_t M, int64_t F, void* out, void* stream);
+/* Padding-free T5 inference: the tower runs on the packed [T, H] rows of "Padding-free BERT inference"
+ * above (drt_t5_embed_bf16 over the gathered real ids as B = 1, L = T; drt_rmsnorm_bf16, the linears
+ * and drt_gated_gelu_new_bf16 take M = T rows; drt_pool_packed_bf16 / drt_unpack_rows_bf16 as they are).
+ * drt_attention_varlen_relbias_forward_bf16: drt_attention_varlen_forward_bf16 plus the relative-
+ *   position bias.  relbias is ONE table per tower, fp32 [heads][2 * bias_len - 1], centred: entry
+ *   (h, k - q + bias_len - 1) is added to the score of query q and key k of every listed sequence
+ *   (the bias depends on k - q alone, so the table serves every length and batch);
+ *   max_len <= bias_len <= 512.  A sequence of n tokens gets, in its rows, the ctx bits that
+ *   drt_attention_forward_bf16 produces for B = 1, L = n with no mask and the L = n table (entries
+ *   bias_len - n .. bias_len + n - 2 of each head's row), when max_len is in n's length class
+ *   (ceil(n / 32) key blocks up to 5, else the streamed form); an all-zero table gives the bits of
+ *   drt_attention_varlen_forward_bf16.  Everything else is that entry's contract: seq_ids (NULL =
+ *   sequences 0 .. n_seqs - 1), rows of unlisted sequences not touched, a length above max_len
+ *   clamped to it, head_dim == 64, no mask, inference only; DRT_EINVAL before any HIP call for a
+ *   bad argument (a NULL relbias included), DRT_OK for n_seqs == 0 after the shape checks.      */
+int drt_attention_varlen_relbias_forward_bf16(const void* qkv, const int32_t* cu_seqlens, const int32_t* seq_ids,
+                                              int64_t n_seqs, int32_t max_len, const float* relbias,
+                                              int32_t bias_len, void* ctx, int32_t heads, int32_t head_dim,
+                                              float scale, void* stream);
 /* T5 encoder training (HF T5EncoderModel under autograd): drt_attention_forward_bf16 /
  * drt_attention_backward_bf16 with relbias and dtable ("Attention" above), and the backwards of
  * T5LayerNorm, the two feed-forward activations and the shared embedding.  The projections use
